@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — walk-steps/sec of the `--cmd randomwalk` hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]    (N > 1: launched by torch.distributed.run)
+
+A plain run does what the headline needs: set-up, W warm-up iterations, the K timed ones, the result line.  `--full` adds
+everything else described below (the request-rate probe and the PMC passes of the roofline, `end_to_end`, `configs`,
+`embedding_stage`, `cpu_baseline`, and at N = 1 under torch.distributed.run the vertex-sharded legs).  `--dump-outputs DIR`
+writes what the last timed iteration computed, as a caller of srw_walk + srw_fetch_paths receives it, to DIR/paths.npy and
+DIR/lens.npy, float64, with the walkers' indices in DIR/walkers.npy (a fixed seeded sample of them when there are more than
+fit in 64 MB).
 
 Headline workload (BASELINE.json metric: "walk-steps/sec ... on 1B-edge RMAT"): RMAT scale-26, edge factor 16
 (1.07 B edge lines -> 2.15 B adjacency entries, 32.8 M present vertices), undirected, p = q = 1,
@@ -9,10 +16,10 @@ walkLength = 80, generated and built into CSR on the device (synthetic, seed 42)
 iteration (numWalks = 1): one walker per present vertex, 81 walk-steps each = 2.66e9 walk-steps.
 Timed region: K walk iterations, inputs (graph + sampling tables) resident in HBM, outputs (paths) left in HBM;
 barrier + torch.cuda.synchronize() on both sides; max over ranks.  Everything the timed region excludes is reported next
-to it: `setup_s` (graph generation + CSR build + sampling tables) and `end_to_end` (one iteration through
+to it: `setup_s` (graph generation + CSR build + sampling tables) and, with --full, `end_to_end` (one iteration through
 srw_walk_and_save: walk + device formatter + PCIe + part files, text bytes per second).
 
-After the headline, with one GPU, `configs` carries the other BASELINE.json configurations that fit one GPU — C2
+With --full, after the headline, with one GPU, `configs` carries the other BASELINE.json configurations that fit one GPU — C2
 (RMAT-20, p = q = 1), C3 (weighted RMAT-24, p = .25 q = 4; Mode R = bit-exact reference sampler, and Mode A = alias tables
 + rejection; the same graph with q = 1), C5's stand-in (directed RMAT-26 ef 27, p = 4 q = .5; Mode R and Mode A) — each with its own value, kernel
 time, setup and roofline.
@@ -338,6 +345,28 @@ def measure(eng, walk_kw, K, W, first_walk=0):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0 - inner_setup * 1e-3
     return steps, dt, kernel_ms, stats, (setup_ms + inner_setup) * 1e-3
+
+
+DUMP_BYTES = 64 << 20
+DUMP_MAX_WALKERS = 65536
+
+
+def dump_outputs(pkg, eng, out_dir):
+    """The engine's last walk as its caller receives it (srw_fetch_paths: paths [walkers][walkLength + 2] with a -1 tail, and
+    lens) -> out_dir/paths.npy, out_dir/lens.npy.  float64: vertex ids of the headline graph exceed float32's 2^24.  More walkers
+    than DUMP_MAX_WALKERS (or than fit in DUMP_BYTES): a sample drawn with a fixed seed, in walker order, the same for the same
+    arguments; out_dir/walkers.npy holds the indices taken."""
+    import numpy as np
+    _, _, n, stride = eng.device_paths()
+    paths = np.empty((n, stride), dtype=np.int32)
+    lens = np.empty(n, dtype=np.int32)
+    eng._ck(pkg.lib().srw_fetch_paths(eng.h, pkg._i32(paths), pkg._i32(lens)))
+    keep = min(n, DUMP_MAX_WALKERS, DUMP_BYTES // ((stride + 2) * 8))
+    rows = np.arange(n) if keep == n else np.sort(np.random.default_rng(20240607).choice(n, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "paths.npy"), paths[rows].astype(np.float64))
+    np.save(os.path.join(out_dir, "lens.npy"), lens[rows].astype(np.float64))
+    np.save(os.path.join(out_dir, "walkers.npy"), rows.astype(np.float64))
 
 
 def run_config(pkg, device, name, scale, ef, weighted, directed, p, q, sampler, K, W, L=80, ceiling=None, plan_walks=0, pmc=False):
@@ -670,6 +699,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: roofline probes, end to end, configs, embedding stage, CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the paths and lengths of the last timed iteration (rank 0's) to DIR/paths.npy, DIR/lens.npy and "
+                         "the walker indices sampled to DIR/walkers.npy (float64, at most 64 MB)")
     ap.add_argument("--scale", type=int, default=26, help="RMAT scale (26 = the 1B-edge headline graph)")
     ap.add_argument("--edge-factor", type=int, default=16)
     ap.add_argument("--walk-length", type=int, default=80)
@@ -688,6 +722,7 @@ def main():
     ap.add_argument("--rccl-leg", type=int, default=0, help=argparse.SUPPRESS)      # child job of an N > 1 run: see main()
     ap.add_argument("--nt-loads", type=int, default=-1, help="-1 auto, 0 cached, 1 nontemporal record loads")
     ap.add_argument("--compact", type=int, default=1, help="0: do not use the 16-byte lattice records")
+    # the four legs below run only with --full (their defaults are what --full does)
     ap.add_argument("--configs", type=int, default=1, help="1 GPU: also run BASELINE configs C2, C3 (Mode R / A), C5 stand-in")
     ap.add_argument("--configs-scale-cap", type=int, default=0, help="tests: run the `configs` plan with every scale capped at this value")
     ap.add_argument("--time-budget", type=float, default=420.0, help="seconds after which no further optional configuration starts")
@@ -702,6 +737,8 @@ def main():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help=argparse.SUPPRESS)     # tests: gloo (chunks staged through host memory)
     ap.add_argument("--share-device", type=int, default=0, help=argparse.SUPPRESS)                     # tests: every rank on device 0 (a one-GPU box)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import _pkg
@@ -800,7 +837,7 @@ def main():
         # the request-rate ceiling of THIS box (about a second; outside the timed region): dependent random 16-byte reads over a
         # table of the size of the headline's record table
         ceiling = None
-        if rank == 0:
+        if rank == 0 and args.full:
             try:
                 rps, gib = eng.probe_request_rate(ne * 16)
                 ceiling = {"reads_per_s": rps, "table_gib": gib}
@@ -825,12 +862,16 @@ def main():
         dt = time.perf_counter() - t0
         total_steps = int(allreduce(steps, dist.ReduceOp.SUM)) if dist is not None else steps
         max_dt = allreduce(dt, dist.ReduceOp.MAX) if dist is not None else dt
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(pkg, eng, args.dump_outputs)
         if rank == 0:
             avg_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
-            try:
-                scan = eng.result_scan_sums()
-            except Exception:
-                scan = None
+            scan = None
+            if args.full:
+                try:
+                    scan = eng.result_scan_sums()
+                except Exception:
+                    scan = None
             out = {
                 "metric": "walk-steps/sec", "value": total_steps / max_dt, "unit": "walk-steps/s", "n_gpus": world,
                 "steps": K, "warmup": W, "ms_per_step": max_dt / max(K, 1) * 1e3, "higher_is_better": True,
@@ -851,7 +892,7 @@ def main():
                             "note": "outside the timed region; one-off per graph / per (p, q)"},
             }
         # ---- the headline kernel's HBM-side counters, taken in this run (child processes; the engine above keeps its graph) -----------
-        if rank == 0 and world == 1 and args.pmc and out is not None:
+        if rank == 0 and world == 1 and args.full and args.pmc and out is not None:
             spec = "%d%s%s" % (args.scale, "w" if args.weighted else "", "d" if args.directed else "")
             pm = pmc_child_pass(out["roofline"]["kernel"].split(" ")[0], [spec, args.p, args.q, args.sampler, 3, args.edge_factor])
             if pm is not None:
@@ -859,7 +900,7 @@ def main():
             else:
                 out["roofline"]["traffic_note"] = "rocprofv3 --pmc child pass unavailable on this box: traffic not measured in this run"
         # ---- end to end: the reference's contract is path FILES --------------------------------------------------------
-        if rank == 0 and world == 1 and args.end_to_end:
+        if rank == 0 and world == 1 and args.full and args.end_to_end:
             e2e = {"what": "srw_walk_and_save, 1 walk iteration: walk kernel + device-side formatter + PCIe + <output>/path/part-00000 on local "
                            "disk — ONE part file, the reference's default (singleOutput = true: Params.scala:21, Main.scala:64-69; bound by one "
                            "inode's buffered writes); `parts_200`: the same with --singleOutput false (rddPartitions = 200 part files, written in "
@@ -898,7 +939,7 @@ def main():
     # between the shards' streams) while the other ranks wait — no collective inside the leg, so a failure in it cannot
     # hang the job or cost the headline line.  --shard-driver rccl runs the one-process-per-GPU driver instead
     # (stellar-random-walk_amd/distributed.py: one RCCL all_to_all_single per super-step).
-    if dist is not None and args.shard in ("both", "vertex"):
+    if dist is not None and args.shard in ("both", "vertex") and (world > 1 or args.full):
         vs = {}
         if rank == 0:
             # Every leg runs in a CHILD job while the ranks of this one wait at a barrier: a fault or a hang on a peer device
@@ -955,7 +996,7 @@ def main():
             out["vertex_sharded"] = vs
 
     if rank == 0:
-        if world == 1 and args.configs:
+        if world == 1 and args.full and args.configs:
             cfgs = []
             plan = [("C2", 20, 16, False, False, 1.0, 1.0, "reference", 10, 1),
                     ("C3 Mode R", 24, 16, True, False, 0.25, 4.0, "reference", 2, 1),
@@ -999,7 +1040,7 @@ def main():
                 except Exception as ex:
                     out["embedding_stage"] = {"error": str(ex)[:200]}
             out["wall_s_before_cpu_baseline"] = time.perf_counter() - T_START
-        if world == 1 and args.cpu_baseline:
+        if world == 1 and args.full and args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         emit(out, args)
     if dist is not None:

@@ -47,7 +47,7 @@ def check_driver_keys(d):
 @pytest.mark.gpu
 def test_single_gpu_line(tmp_path):
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "16", "--steps", "3", "--warmup", "1", "--configs", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scale", "16", "--steps", "3", "--warmup", "1", "--configs", "0",
                         "--end-to-end", "1", "--cpu-baseline", "1", "--cpu-scale", "10", "--cpu-sources", "64", "--cpu-walk-length", "10",
                         "--detail", detail],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -72,11 +72,41 @@ def test_single_gpu_line(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full: the headline and nothing of the optional legs.  --dump-outputs: the paths and lengths of the last timed
+    iteration (walk index W + K - 1), as a caller of srw_walk + srw_fetch_paths receives them; RMAT-17 has more walkers than the
+    dump keeps, so a sample is taken."""
+    import numpy as np
+    import helpers
+    out, detail = tmp_path / "outputs", str(tmp_path / "detail.json")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "17", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out), "--detail", detail],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json(r.stdout)
+    check_driver_keys(d)
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - d["config"]["walk_steps_per_bench_step"] / (d["ms_per_step"] * 1e-3)) < 1e-4 * d["value"]
+    full = json.load(open(detail))
+    for k in ("end_to_end", "configs", "embedding_stage", "cpu_baseline", "vertex_sharded"):
+        assert k not in full, k
+    assert "request_rate_ceiling" not in full["roofline"] and "algorithmic_bytes_scan" not in full["roofline"]
+    dump = {k: np.load(str(out / (k + ".npy"))) for k in ("paths", "lens", "walkers")}
+    assert all(a.dtype == np.float64 for a in dump.values()) and sum(a.nbytes for a in dump.values()) <= 64 << 20
+    rows = dump["walkers"].astype(np.int64)
+    with helpers.pkg().Engine(device=0) as eng:
+        eng.generate_rmat(17, 16 << 17, seed=42)
+        paths, lens, _ = eng.walk(p=1.0, q=1.0, walk_length=80, num_walks=1, seed=42, first_walk=3)
+    assert len(rows) < len(lens) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(dump["paths"], paths[rows]) and np.array_equal(dump["lens"], lens[rows])
+
+
+@pytest.mark.gpu
 def test_single_gpu_line_with_every_config_stays_small(tmp_path):
     """The form the driver meets (--configs 1: ten more configurations, the CPU plan) on graphs capped at scale 13: the one
     stdout line must still fit, and every configuration must be in its summary."""
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "14", "--steps", "2", "--warmup", "1", "--configs", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scale", "14", "--steps", "2", "--warmup", "1", "--configs", "1",
                         "--configs-scale-cap", "13", "--end-to-end", "1", "--cpu-baseline", "1", "--cpu-scale", "10", "--cpu-sources", "64",
                         "--cpu-walk-length", "10", "--detail", detail],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1800)
@@ -110,11 +140,52 @@ def test_compact_line_sheds_before_it_overflows():
     assert len(line) <= b.LINE_LIMIT == LINE_LIMIT and "roofline" in d and "cpu_baseline" in d and "algorithmic_bytes_formula" not in d["roofline"]
 
 
+def test_dump_outputs_keeps_a_fixed_sample_within_64_mb(tmp_path):
+    """dump_outputs over a stand-in engine whose result holds more walkers than fit: the same sorted sample every time, the rows
+    the engine returned for those walkers, float64, 64 MB at most."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    n, stride = 300000, 82
+
+    class Lib:
+        def srw_fetch_paths(self, h, paths, lens):
+            paths[:] = np.arange(n, dtype=np.int32)[:, None] * 3 + np.arange(stride, dtype=np.int32)
+            lens[:] = np.arange(n, dtype=np.int32) % 81
+            return 0
+
+    class Pkg:
+        lib = staticmethod(Lib)
+        _i32 = staticmethod(lambda a: a)
+
+    class Eng:
+        h = None
+
+        def device_paths(self):
+            return 0, 0, n, stride
+
+        def _ck(self, rc):
+            assert rc == 0
+
+    dumps = []
+    for k in range(2):
+        b.dump_outputs(Pkg, Eng(), str(tmp_path / str(k)))
+        dumps.append({a: np.load(str(tmp_path / str(k) / (a + ".npy"))) for a in ("paths", "lens", "walkers")})
+    d = dumps[0]
+    assert all(np.array_equal(d[a], dumps[1][a]) and d[a].dtype == np.float64 for a in d)
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20 and len(d["walkers"]) == b.DUMP_MAX_WALKERS
+    rows = d["walkers"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+    assert np.array_equal(d["paths"], rows[:, None] * 3 + np.arange(stride)) and np.array_equal(d["lens"], rows % 81)
+
+
 @pytest.mark.gpu
 def test_torchrun_one_rank_adds_the_vertex_sharded_leg():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "16", "--steps", "2", "--warmup", "1",
+                        "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--scale", "16", "--steps", "2", "--warmup", "1",
                         "--configs", "0", "--end-to-end", "0", "--cpu-baseline", "0", "--biased-leg", "0"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

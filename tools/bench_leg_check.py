@@ -1,5 +1,5 @@
-import sys, json
-sys.path.insert(0, "/root/repo")
+import json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, _pkg, bench
 pkg = _pkg.load(); torch.zeros(1, device="cuda")
 for (n, p, q) in [("c3q1", 0.25, 1.0), ("c3", 0.25, 4.0)]:
