@@ -311,6 +311,17 @@ def write_paths(paths, lens, output_dir, n_parts=1):
                                      n_parts))
 
 
+def threads():
+    """Thread count for the oracle's pools: the CPUs this process may run on, capped by OMP_NUM_THREADS when that is set
+    (os.cpu_count() reports the whole machine's).  No result depends on it."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        cap = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        cap = 0
+    return max(1, min(n, cap) if cap > 0 else n)
+
+
 def rmat_edges(scale, n_edges, seed=42, first=0):
     s = np.zeros(n_edges, dtype=np.int32)
     d = np.zeros(n_edges, dtype=np.int32)
@@ -320,7 +331,7 @@ def rmat_edges(scale, n_edges, seed=42, first=0):
         return s, d
     # edge i is a pure function of (seed, i): slices on threads (ctypes releases the GIL)
     import concurrent.futures as cf
-    nt = min(64, os.cpu_count() or 1)
+    nt = threads()
     step = -(-n_edges // (nt * 4))
     def work(lo):
         n = min(step, n_edges - lo)

@@ -556,6 +556,14 @@ __global__ void k_rows_max(unsigned long long *__restrict__ acc, const unsigned 
     acc[i] = (unsigned long long)(a > b ? a : b);
   }
 }
+// rows a link cannot describe (shard_link_of clamps the degree to CFO_NDEG_MAX and the offset to 36 bits): a linked walker
+// seeded on such a row would sample only a prefix of it
+__global__ void k_rows_unlinkable(const Row *__restrict__ rows, int64_t n_slots, unsigned long long *count) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_slots; i += (int64_t)gridDim.x * blockDim.x) {
+    const Row r = rows[i];
+    if (r.deg > (int32_t)CFO_NDEG_MAX || r.off >= ((int64_t)1 << 36)) atomicAdd(count, 1ull);
+  }
+}
 }  // namespace
 
 void shard_rows_export(srw_handle *h, void *d_rows, int64_t n_slots) {
@@ -589,6 +597,18 @@ bool shard_rows_commit(srw_handle *h, const void *d_rows_all, int64_t n_slots) {
   SRW_HIP(hipMemcpyAsync(g.rows_all.p, d_rows_all, (size_t)n_slots * sizeof(Row), hipMemcpyDeviceToDevice, h->stream));
   if (g.n_entries == 0) { SRW_HIP(hipStreamSynchronize(h->stream)); g.cfo_linked = true; return true; }
   DevBuf<unsigned long long> esc; esc.alloc(1);
+  // The records escape when a NEIGHBOUR row is too long for a link; a walker's seed link is its own row's (k_sh_seed), so a
+  // too-long row that no record names (a source without in-edges) needs the same escape
+  {
+    unsigned long long n_bad = 0;
+    SRW_HIP(hipMemsetAsync(esc.p, 0, 8, h->stream));
+    const int blocks = (int)std::min<int64_t>(std::max<int64_t>((n_slots + 255) / 256, 1), 256 * 32);
+    hipLaunchKernelGGL(k_rows_unlinkable, dim3(blocks), dim3(256), 0, h->stream, g.rows_all.p, n_slots, esc.p);
+    SRW_HIP(hipGetLastError());
+    SRW_HIP(hipMemcpyAsync(&n_bad, esc.p, 8, hipMemcpyDeviceToHost, h->stream));
+    SRW_HIP(hipStreamSynchronize(h->stream));
+    if (n_bad != 0) { g.rows_all.release(); return false; }
+  }
   if (g.has_cfo) {      // world == 1 after a replicated walk: the local links are the owners' links
     if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_shard_rows_commit: the handle already holds an unsharded compact table");
     SRW_HIP(hipStreamSynchronize(h->stream)); g.cfo_linked = true; return true;

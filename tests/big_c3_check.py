@@ -4,15 +4,19 @@ a 2 000-vertex sample) are compared bit for bit with the CPU ORACLE.  The oracle
 DEVICE paths, rebuilt on the host from the same (seed, edge index) stream (the oracle's generator, 256 M lines at a time, lines kept in
 stream order — rows of prev and curr alike, so computeSecondOrderWeights sees what the reference would).  A deviation sends the oracle's
 walker into a row that was not collected (partial or empty), which shows as a mismatch: the check cannot pass on the device's say-so.
-Run by tests/test_gpu_full_size.py:  python tests/big_c3_check.py [scale]"""
+Run by tests/test_gpu_full_size.py with `every` (tests/big_every_walker_check.py's check on the same graph and tables):
+    python tests/big_c3_check.py [scale] [every]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import _pkg
 import oracle_py as oracle
+from big_every_walker_check import every_walker
 from helpers import rmat_weights_np
 
+every = "every" in sys.argv[1:]          # also every walker through the other samplers (big_every_walker_check.py), same graph and tables
+sys.argv = [a for a in sys.argv if a != "every"]
 scale = int(sys.argv[1]) if len(sys.argv) > 1 else 24
 n_edges = 16 << scale
 # (p, q, walkLength, sampled walkers): the configuration's own case at its walkLength 80 over 20 000 walkers (VERDICT r05 item 3: the rare paths
@@ -34,6 +38,9 @@ dev = []
 on_path = np.zeros(1 << scale, dtype=bool)
 for (p, q, L, _), pick in zip(CASES, picks):
     paths, lens, st = eng.walk(p=p, q=q, walk_length=L, seed=2026)
+    if every and (p, q, L) == (0.25, 4.0, 80):
+        ok_every = every_walker(eng, p, q, ref=(paths, lens, st))
+        print("every walker at full size (c3):", "parity OK" if ok_every else "PARITY FAILED", flush=True)
     sp, sl = paths[pick].copy(), lens[pick].copy()
     on_path[sp[sp >= 0]] = True
     dev.append((sp, sl, st))
@@ -53,11 +60,11 @@ ok = True
 for (p, q, L, _), pick, (sp, sl, st) in zip(CASES, picks, dev):
     t = time.time()
     src = verts[pick].astype(np.int32)
-    rp, rl, _ = g.walk(sources=src, p=p, q=q, walk_length=L, seed=2026, threads=min(128, os.cpu_count() or 8))
+    rp, rl, _ = g.walk(sources=src, p=p, q=q, walk_length=L, seed=2026, threads=oracle.threads())
     same = bool(np.array_equal(sp, rp) and np.array_equal(sl, rl))
     ok &= same
     ss = {k: v for k, v in st["strategy_steps"].items() if v}
     print("p=%g q=%g L=%d: %d sampled walkers (longest start row %d) %s; oracle %.0f s; device kernel %.0f ms, setup %.0f ms, %s"
           % (p, q, L, len(src), int(degs.max()), "IDENTICAL" if same else "MISMATCH", time.time() - t, st["kernel_ms"], st["setup_ms"], ss), flush=True)
 print("config 3 at full size:", "parity OK" if ok else "PARITY FAILED")
-sys.exit(0 if ok else 1)
+sys.exit(0 if ok and (not every or ok_every) else 1)

@@ -49,7 +49,7 @@ for lo in range(0, n_edges, BLOCK):
     del s_, d_, keep
 fs = np.concatenate(fs); fd = np.concatenate(fd)
 g = oracle.Graph.from_coo(fs, fd, None, directed=False)
-rp, rl, _ = g.walk(sources=src, p=1.0, q=1.0, walk_length=L, seed=2026, first_walk=1, threads=min(64, os.cpu_count() or 8))
+rp, rl, _ = g.walk(sources=src, p=1.0, q=1.0, walk_length=L, seed=2026, first_walk=1, threads=oracle.threads())
 same_or = bool(np.array_equal(paths[pick], rp) and np.array_equal(lens[pick], rl))
 ok = same_or
 print("oracle: %d sampled walkers (longest start row %d), rows of %d path vertices rebuilt from the edge stream (%d of %d lines kept): %s (%.0f s)"
