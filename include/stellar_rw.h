@@ -209,6 +209,30 @@ int32_t srw_walk_to_host(srw_handle *h, const srw_walk_params *params, int32_t *
  * Fails with SRW_ERR_EXISTS before any work if <output_dir>/path exists. */
 int32_t srw_walk_and_save(srw_handle *h, const srw_walk_params *params, const char *output_dir, int32_t n_parts,
                           int32_t write_crc, srw_walk_stats *stats, int64_t *dead_ends_per_iteration);
+/* ---- walks from a list of start vertices (whole-graph handles) --------------------------------
+ * No reference counterpart: RandomWalk.randomWalk always seeds one walker per vertex (initFirstStep, RandomWalk.scala:51-66).
+ * Walk from these vertices instead of from every present vertex.  ids[n] (host) are vertex ids as the input
+ * spelled them, in any order, duplicates allowed; the list is copied.  Until srw_clear_sources or the next
+ * graph load, srw_walk / srw_walk_to_host / srw_walk_and_save seed num_walks * n walkers:
+ * walker index = iteration * n + position in the list — every buffer size and output order documented above in
+ * terms of nVertices / rank(vertex) then reads n / position in the list (iteration major, then LIST order).  A draw is
+ * keyed by (seed, iteration, source id, step), never by the walker's index: the path of (iteration, v) is the very row the
+ * full walk produces for it, and a duplicate entry repeats its path.  n == 0 is a valid list (zero walkers).  Which sampling
+ * tables a call builds does not depend on the list (SRW_WALK_NO_EDGE_TABLES / _NO_HUB_BITMAPS give a cheap cold start).
+ * SRW_ERR_INVALID, with the handle's previous list (or none) left in force, if an id is not a vertex of the
+ * loaded graph (the message names the first such id and its position), if no graph is loaded, on a sharded
+ * handle (world > 1) or while population 1 is selected.  A vertex of the graph is what srw_graph_vertices lists:
+ * one that only appears as the destination of a directed edge is a vertex (its walk is the one-entry path).
+ * The srw_shard_* / srw_cluster_* family ignores the list. */
+int32_t srw_set_sources(srw_handle *h, const int32_t *ids, int64_t n);
+/* The same with the ids already in device memory on the handle's GPU (a tensor of a training loop): copied and
+ * checked on the handle's stream — the caller has made sure that the ids are written before the call; one 8-byte
+ * read-back reports an unknown id. */
+int32_t srw_set_sources_device(srw_handle *h, const void *d_ids, int64_t n);
+int32_t srw_clear_sources(srw_handle *h);
+/* *n = length of the list in force, -1 when there is none (walks start from every vertex). */
+int32_t srw_sources(const srw_handle *h, int64_t *n);
+
 /* Pinned (page-locked) host memory for srw_walk_to_host / srw_fetch_paths destinations. */
 int32_t srw_host_alloc(size_t bytes, void **out);
 void srw_host_free(void *p);
@@ -218,7 +242,8 @@ int32_t srw_fetch_paths(const srw_handle *h, int32_t *paths, int32_t *lens);
 int32_t srw_device_paths(const srw_handle *h, void **d_paths, void **d_lens, int64_t *n_walkers, int32_t *stride);
 /* Replaces RandomWalk.save (M/algorithm/RandomWalk.scala:234-241) + Property.pathSuffix: writes
  * <output_dir>/path/part-00000.. (TAB-joined ids, one '\n' per path) and _SUCCESS; canonical line
- * order (walk iteration major, source id ascending).  write_crc != 0 adds Hadoop .crc side files.
+ * order (walk iteration major, source id ascending; after srw_set_sources: iteration major, then list order).
+ * write_crc != 0 adds Hadoop .crc side files.
  * The text is formatted on the GPU from the device-resident result (SRW_HOST_FORMATTER=1: on host threads). */
 int32_t srw_write_paths(const srw_handle *h, const char *output_dir, int32_t n_parts, int32_t write_crc);
 
@@ -395,6 +420,11 @@ int32_t srw_rng_uniform(srw_handle *h, uint32_t seed, const uint32_t *iter, cons
  * (released by srw_free).  Used by the CLI and by tests of the parse rules. */
 int32_t srw_parse_edgelist(const char *path, int32_t weighted, int32_t partitioned, int32_t **src,
                            int32_t **dst, float **w, int32_t **pid, int64_t *n_lines, char *err, size_t errlen);
+/* The --sources file of the CLI: vertex ids separated by white space / line ends, each token read by the rule of an edge
+ * list's id column (Integer.parseInt, Unicode decimal digits included).  *ids (released by srw_free) holds *n ids in file
+ * order; an empty file gives n = 0.  SRW_ERR_PARSE for a token that is no int32 ("line N: NumberFormatException ..."),
+ * SRW_ERR_IO for a missing file ("Input path does not exist: ..."); the message goes to err. */
+int32_t srw_parse_sources(const char *path, int32_t **ids, int64_t *n, char *err, size_t errlen);
 void srw_free(void *p);
 /* RandomWalk.save on host-resident paths (M/algorithm/RandomWalk.scala:234-241): same files as
  * srw_write_paths, for callers that assembled several walk calls themselves. */

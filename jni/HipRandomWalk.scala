@@ -13,8 +13,13 @@ import au.csiro.data61.randomwalk.common.{Params, Property}
   *
   * `seed` keys the Philox stream (walk iteration, source vertex, step index) — paths do not depend on scheduling, GPU
   * count or sharding; `constR` is the reference tests' injected `nextFloat = () => r`.
+  *
+  * `sources` (no counterpart in the reference, whose randomWalk seeds one walker per vertex): walk from these vertex ids only, in
+  * this order, duplicates allowed — walker = iteration * sources.length + position.  An id that is no vertex of the graph is an
+  * IllegalArgumentException.  Not available to executeSharded.
   */
-class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None, device: Int = 0)
+class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None, device: Int = 0,
+                    sources: Option[Array[Int]] = None)
   extends Serializable {
 
   System.loadLibrary("stellar_rw_jni") // links libstellar_rw.so
@@ -40,6 +45,14 @@ class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None
                                          seed: Int, output: String, parts: Int): Array[Long]
   @native private def fetchPaths(h: Long, lens: Array[Int]): Array[Int]
   @native private def neighbors(h: Long, v: Int): Array[Int]
+  @native private def setSources(h: Long, ids: Array[Int]): Int
+  @native private def clearSources(h: Long): Int
+
+  /** after loadEdgeList: the walkers of one iteration — the list's length, or every vertex */
+  private def applySources(h: Long): Long = sources match {
+    case Some(ids) => setSources(h, ids).toLong
+    case None => clearSources(h); nVertices
+  }
 
   var nVertices: Long = 0L
   var nEdges: Long = 0L
@@ -54,6 +67,7 @@ class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None
       nEdges = e
       println(s"edges: $nEdges")
       println(s"vertices: $nVertices")
+      applySources(h)
       val dead = walkAndSave(h, config.p.toFloat, config.q.toFloat, config.walkLength, config.numWalks,
         constR.getOrElse(0f), constR.isDefined, seed, output, partitions)
       for (i <- 0 until config.numWalks) {
@@ -70,6 +84,7 @@ class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None
     * transferWalkersToTheirPartitions (RandomWalk.scala:186-192).  Same files as execute().
     */
   def executeSharded(output: String, partitions: Int, devices: Seq[Int]): Unit = {
+    require(sources.isEmpty, "the vertex-sharded walk starts from every vertex: no sources")
     val Array(v, e, _, dead) = walkAndSaveSharded((devices :+ -1).toArray, config.input, config.directed, config.weighted,
       config.partitioned, config.rddPartitions, config.p.toFloat, config.q.toFloat, config.walkLength,
       config.numWalks, constR.getOrElse(0f), constR.isDefined, seed, output, partitions)
@@ -95,6 +110,7 @@ class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None
       nEdges = e
       println(s"edges: $nEdges")
       println(s"vertices: $nVertices")
+      applySources(h)
       planWalks(h, config.numWalks)
       walkAll(h, config.p.toFloat, config.q.toFloat, config.walkLength, config.numWalks,
         constR.getOrElse(0f), constR.isDefined, seed)
@@ -112,12 +128,13 @@ class HipRandomWalk(config: Params, seed: Int = 42, constR: Option[Float] = None
       config.partitioned, config.rddPartitions)
     nVertices = v
     nEdges = e
+    val perIteration = applySources(h).toInt
     val stride = config.walkLength + 2
     val its = (0 until config.numWalks).iterator.flatMap { i =>
       walk(h, config.p.toFloat, config.q.toFloat, config.walkLength, i, constR.getOrElse(0f), constR.isDefined, seed)
-      val lens = new Array[Int](nVertices.toInt)
+      val lens = new Array[Int](perIteration)
       val flat = fetchPaths(h, lens)
-      (0 until nVertices.toInt).iterator.map(w => java.util.Arrays.copyOfRange(flat, w * stride, w * stride + lens(w)))
+      (0 until perIteration).iterator.map(w => java.util.Arrays.copyOfRange(flat, w * stride, w * stride + lens(w)))
     }
     new Iterator[Array[Int]] {
       private var open = true

@@ -255,6 +255,29 @@ JNIEXPORT jintArray JNICALL FN(neighbors)(JNIEnv *env, jobject self, jlong hh, j
   return a;
 }
 
+/* srw_set_sources: the walks that follow start from these vertex ids only, in this order (duplicates allowed); returns the list's
+ * length.  An id that is no vertex of the loaded graph: IllegalArgumentException naming it, the previous list stays in force. */
+JNIEXPORT jint JNICALL FN(setSources)(JNIEnv *env, jobject self, jlong hh, jintArray ids) {
+  (void)self;
+  /* the JVM's own array length bounds the read; the ids go through a C buffer (Get*ArrayRegion), not a critical region */
+  const jsize n = ids ? (*env)->GetArrayLength(env, ids) : 0;
+  jint *tmp = (jint *)malloc((size_t)(n > 0 ? n : 1) * sizeof(jint));
+  if (!tmp) { throw_status(env, SRW_ERR_NOMEM, NULL); return 0; }
+  if (n > 0) (*env)->GetIntArrayRegion(env, ids, 0, n, tmp);
+  const int32_t rc = srw_set_sources(H(hh), (const int32_t *)tmp, (int64_t)n);
+  free(tmp);
+  if (rc != SRW_OK) { throw_status(env, rc, H(hh)); return 0; }
+  return (jint)n;
+}
+
+/* srw_clear_sources: back to one walker per present vertex and iteration */
+JNIEXPORT jint JNICALL FN(clearSources)(JNIEnv *env, jobject self, jlong hh) {
+  (void)self;
+  const int32_t rc = srw_clear_sources(H(hh));
+  if (rc != SRW_OK) throw_status(env, rc, H(hh));
+  return 0;
+}
+
 JNIEXPORT jstring JNICALL FN(version)(JNIEnv *env, jclass cls) {
   (void)cls;
   return (*env)->NewStringUTF(env, srw_version());

@@ -87,14 +87,14 @@ STRATEGIES = ("edge_table", "p1", "p2", "w", "p3", "scan", "prefix", "chain", "e
 EXPORTS = [
     "srw_create", "srw_destroy", "srw_last_error", "srw_set_stream", "srw_plan_walks", "srw_load_edgelist", "srw_load_coo",
     "srw_load_adjacency", "srw_generate_rmat", "srw_graph_stats", "srw_graph_vertices", "srw_graph_neighbors",
-    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
+    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
     "srw_shard_capacity", "srw_shard_vertex_ranks", "srw_shard_layout_for", "srw_shard_begin", "srw_shard_superstep",
     "srw_shard_flush", "srw_shard_finish", "srw_shard_rows_count", "srw_shard_rows_export", "srw_shard_rows_merge",
     "srw_shard_rows_commit", "srw_shard_rows_release", "srw_device_alloc", "srw_device_free", "srw_cluster_create", "srw_cluster_destroy", "srw_cluster_last_error",
     "srw_cluster_shard", "srw_cluster_load_edgelist", "srw_cluster_load_coo", "srw_cluster_generate_rmat",
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
     "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
-    "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
+    "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
 
 _lib = None
@@ -130,6 +130,10 @@ def lib():
     L.srw_walk.argtypes = [vp, C.POINTER(WalkParams), C.POINTER(WalkStats)]
     L.srw_walk_to_host.argtypes = [vp, C.POINTER(WalkParams), i32p, i32p, C.POINTER(WalkStats)]
     L.srw_walk_and_save.argtypes = [vp, C.POINTER(WalkParams), C.c_char_p, C.c_int32, C.c_int32, C.POINTER(WalkStats), i64p]
+    L.srw_set_sources.argtypes = [vp, i32p, C.c_int64]
+    L.srw_set_sources_device.argtypes = [vp, vp, C.c_int64]
+    L.srw_clear_sources.argtypes = [vp]
+    L.srw_sources.argtypes = [vp, i64p]
     L.srw_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.srw_host_free.argtypes = [vp]
     L.srw_host_free.restype = None
@@ -181,6 +185,7 @@ def lib():
     L.srw_rng_uniform.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, C.c_int64, f32p]
     L.srw_parse_edgelist.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(i32p), C.POINTER(i32p),
                                      C.POINTER(f32p), C.POINTER(i32p), i64p, C.c_char_p, C.c_size_t]
+    L.srw_parse_sources.argtypes = [C.c_char_p, C.POINTER(i32p), i64p, C.c_char_p, C.c_size_t]
     L.srw_free.argtypes = [vp]
     L.srw_free.restype = None
     L.srw_save_paths.argtypes = [i32p, i32p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_int32]
@@ -218,6 +223,19 @@ def parse_edgelist(path, weighted=True, partitioned=False):
     out = tuple(np.ctypeslib.as_array(x, shape=(max(k, 1),))[:k].copy() for x in (s, d, w, p))
     for x in (s, d, w, p):
         L.srw_free(x)
+    return out
+
+
+def parse_sources(path):
+    """Host-only: the ids of a --sources file (white-space separated, the edge list's id rule), in file order."""
+    L = lib()
+    ids, n = C.POINTER(C.c_int32)(), C.c_int64(0)
+    err = C.create_string_buffer(512)
+    rc = L.srw_parse_sources(os.fsencode(path), C.byref(ids), C.byref(n), err, 512)
+    if rc != OK:
+        raise SrwError(rc, err.value.decode(errors="replace"))
+    out = np.ctypeslib.as_array(ids, shape=(max(n.value, 1),))[:n.value].copy()
+    L.srw_free(ids)
     return out
 
 
@@ -369,6 +387,57 @@ class Engine:
         self._ck(lib().srw_alias_row(self.h, v, _f32(prob), _i32(alias), n.value, C.byref(n), C.byref(reg)))
         return reg.value, prob[:n.value], alias[:n.value]
 
+    # ---- start vertices ----
+    def set_sources(self, ids):
+        """Walk from these vertex ids (any order, duplicates allowed) instead of from every vertex, until clear_sources() or the
+        next load: walker index = iteration * len(ids) + position.  A numpy array / sequence goes through the host entry point; an
+        object with data_ptr() and is_cuda (a torch tensor on the handle's device) through the device one — it must be int32 and
+        contiguous, else TypeError."""
+        if hasattr(ids, "data_ptr") and hasattr(ids, "is_cuda"):
+            if "int32" not in str(ids.dtype) or ids.dim() != 1 or not ids.is_contiguous():
+                raise TypeError("set_sources: a tensor of ids must be one-dimensional, int32 and contiguous (got %s)" % ids.dtype)
+            if ids.is_cuda:
+                import torch
+                torch.cuda.current_stream(ids.device).synchronize()      # the ids are written before the handle's stream reads them
+                self._ck(lib().srw_set_sources_device(self.h, C.c_void_p(ids.data_ptr()), int(ids.numel())))
+                self._src_ids = ids.clone()                              # what _with_sources restores
+                return self
+            ids = ids.numpy()
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError("set_sources: vertex ids must be integers (got %s)" % a.dtype)
+        if a.size and (int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1):
+            raise ValueError("set_sources: a vertex id is outside int32")
+        a = np.array(a.reshape(-1), dtype=np.int32)                      # (a copy: the caller may reuse its array)
+        self._ck(lib().srw_set_sources(self.h, _i32(a) if a.size else None, a.size))
+        self._src_ids = a
+        return self
+
+    def clear_sources(self):
+        self._ck(lib().srw_clear_sources(self.h))
+        self._src_ids = None
+        return self
+
+    def sources_len(self):
+        """Length of the list in force, None when there is none (walks start from every vertex)."""
+        n = C.c_int64(0)
+        self._ck(lib().srw_sources(self.h, C.byref(n)))
+        return None if n.value < 0 else n.value
+
+    def _with_sources(self, sources, call):
+        """call() with `sources` as the list in force; the state from before (a list, or none) is back afterwards."""
+        if sources is None:
+            return call()
+        before = getattr(self, "_src_ids", None) if self.sources_len() is not None else None    # (a load clears the handle's list)
+        self.set_sources(sources)
+        try:
+            return call()
+        finally:
+            if before is None:
+                self.clear_sources()
+            else:
+                self.set_sources(before)
+
     # ---- walk ----
     @staticmethod
     def params(p=1.0, q=1.0, walk_length=80, num_walks=1, first_walk=0, rng="philox", const_r=0.0, seed=42,
@@ -381,8 +450,11 @@ class Engine:
                           RNG_CONST if rng == "const" else RNG_PHILOX, np.float32(const_r), seed, sampler,
                           (WALK_FORCE_GENERAL if force_general else 0) | (0 if nt_loads is None else WALK_NT_LOADS if nt_loads else WALK_CACHED_LOADS) | (occ << 8) | (0 if compact else WALK_NO_COMPACT) | (0 if prefix else WALK_NO_PREFIX) | (0 if edge_hash else WALK_NO_EDGE_HASH) | (0 if binned else WALK_NO_BINNED) | (0 if hub_bitmaps else WALK_NO_HUB_BITMAPS) | (WALK_DEVICE_FORMAT if device_format else 0) | (binned_tune << 12) | (0 if edge_tables else WALK_NO_EDGE_TABLES) | (WALK_EDGE_TABLES_ALL if edge_tables_all else 0))
 
-    def walk(self, fetch=True, **kw):
-        """Runs srw_walk.  Returns (paths [nWalkers, L+2] int32 (-1 tail), lens, stats dict) or just stats."""
+    def walk(self, fetch=True, sources=None, **kw):
+        """Runs srw_walk.  Returns (paths [nWalkers, L+2] int32 (-1 tail), lens, stats dict) or just stats.
+        sources=ids: from these vertices only, for this call (set_sources before, the previous state back afterwards)."""
+        if sources is not None:
+            return self._with_sources(sources, lambda: self.walk(fetch=fetch, **kw))
         P = self.params(**kw)
         st = WalkStats()
         self._ck(lib().srw_walk(self.h, C.byref(P), C.byref(st)))
@@ -393,11 +465,15 @@ class Engine:
         self._ck(lib().srw_fetch_paths(self.h, _i32(paths), _i32(lens)))
         return paths[:st.n_walkers], lens[:st.n_walkers], st.as_dict()
 
-    def walk_to_host(self, pinned=True, **kw):
+    def walk_to_host(self, pinned=True, sources=None, **kw):
         """srw_walk_to_host: all num_walks iterations streamed into host buffers (kernel i overlaps the copy of i-1).
         Returns (paths, lens, stats); with pinned=True the arrays are copies of pinned staging memory."""
+        if sources is not None:
+            return self._with_sources(sources, lambda: self.walk_to_host(pinned=pinned, **kw))
         P = self.params(**kw)
-        nv = self.num_vertices
+        nv = self.sources_len()                 # walkers per iteration: the list in force, else every vertex
+        if nv is None:
+            nv = self.num_vertices
         n, stride = P.num_walks * nv, P.walk_length + 2
         st = WalkStats()
         if pinned:
@@ -420,8 +496,10 @@ class Engine:
             paths, lens = paths[:n], lens[:n]
         return paths, lens, st.as_dict()
 
-    def walk_and_save(self, output_dir, n_parts=1, write_crc=False, **kw):
+    def walk_and_save(self, output_dir, n_parts=1, write_crc=False, sources=None, **kw):
         """srw_walk_and_save: Main.doRandomWalk fused and streamed.  Returns (stats, dead_ends_per_iteration)."""
+        if sources is not None:
+            return self._with_sources(sources, lambda: self.walk_and_save(output_dir, n_parts=n_parts, write_crc=write_crc, **kw))
         P = self.params(**kw)
         st = WalkStats()
         dead = (C.c_int64 * max(P.num_walks, 1))()

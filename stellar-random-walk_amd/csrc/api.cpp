@@ -176,6 +176,8 @@ static void need_population0(const srw_handle *h, const char *what) {
     throw srw::Error(SRW_ERR_INVALID, std::string(what) + ": population 1 is selected on this handle (srw_shard_select(h, 0) first)");
 }
 
+static void clear_sources(srw_handle *h) { h->n_sources = -1; h->src_verts.release(); }
+
 int32_t srw_set_stream(srw_handle *h, void *hip_stream) {
   if (!h) return SRW_ERR_INVALID;
   return guarded(h, [&] {
@@ -198,6 +200,7 @@ int32_t srw_load_edgelist(srw_handle *h, const char *path, int32_t directed, int
   if (!h) return SRW_ERR_INVALID;
   return guarded(h, [&] {
     need_population0(h, "srw_load_edgelist");
+    clear_sources(h);                 // a list of start vertices belongs to the graph it was checked against
     need(path != nullptr, "path is null");
     const auto t0 = std::chrono::steady_clock::now();
     // two integer columns and nothing unusual: tokenized on the device (edgelist_device.hip); anything else: below
@@ -231,6 +234,7 @@ int32_t srw_load_coo(srw_handle *h, const int32_t *src, const int32_t *dst, cons
   if (!h) return SRW_ERR_INVALID;
   return guarded(h, [&] {
     need_population0(h, "srw_load_coo");
+    clear_sources(h);                 // a list of start vertices belongs to the graph it was checked against
     need(n_lines == 0 || (src && dst), "src/dst are null");
     load_lines(h, src, dst, w, pid, n_lines, directed != 0);
   });
@@ -241,6 +245,7 @@ int32_t srw_load_adjacency(srw_handle *h, const int32_t *vids, const int64_t *of
   if (!h) return SRW_ERR_INVALID;
   return guarded(h, [&] {
     need_population0(h, "srw_load_adjacency");
+    clear_sources(h);                 // a list of start vertices belongs to the graph it was checked against
     need(vids && offs && (ids || offs[n_rows] == 0), "null argument");
     build_graph_from_host_rows(h, vids, offs, n_rows, ids, w);
     h->g.part_of.clear();
@@ -261,6 +266,7 @@ int32_t srw_generate_rmat(srw_handle *h, int32_t scale, int64_t n_edges, uint32_
   if (!h) return SRW_ERR_INVALID;
   return guarded(h, [&] {
     need_population0(h, "srw_generate_rmat");
+    clear_sources(h);                 // a list of start vertices belongs to the graph it was checked against
     DevBuf<int32_t> d_src, d_dst; DevBuf<float> d_w;
     if (h->cfg.world > 1 && !getenv("SRW_BUILD_WHOLE")) {
       // a shard generates the stream block by block (edge i is a pure function of (seed, i)) and keeps what it owns
@@ -372,6 +378,27 @@ int32_t srw_walk_and_save(srw_handle *h, const srw_walk_params *params, const ch
     need(params && output_dir, "null argument");
     run_walk_and_save(h, *params, output_dir, n_parts, write_crc != 0, stats, dead_ends_per_iteration);
   });
+}
+
+int32_t srw_set_sources(srw_handle *h, const int32_t *ids, int64_t n) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] { need_population0(h, "srw_set_sources"); set_sources(h, ids, nullptr, n); });
+}
+
+int32_t srw_set_sources_device(srw_handle *h, const void *d_ids, int64_t n) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] { need_population0(h, "srw_set_sources_device"); set_sources(h, nullptr, d_ids, n); });
+}
+
+int32_t srw_clear_sources(srw_handle *h) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] { need_population0(h, "srw_clear_sources"); clear_sources(h); });
+}
+
+int32_t srw_sources(const srw_handle *h, int64_t *n) {
+  if (!h || !n) return SRW_ERR_INVALID;
+  *n = h->n_sources >= 0 ? h->n_sources : -1;
+  return SRW_OK;
 }
 
 int32_t srw_host_alloc(size_t bytes, void **out) {
@@ -649,6 +676,26 @@ int32_t srw_parse_edgelist(const char *path, int32_t weighted, int32_t partition
     if (w) *w = (float *)dup(L.w.data(), 4);
     if (pid) *pid = (int32_t *)dup(L.pid.data(), 4);
     *n_lines = (int64_t)n;
+    return SRW_OK;
+  } catch (const Error &e) {
+    if (err && errlen) snprintf(err, errlen, "%s", e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    if (err && errlen) snprintf(err, errlen, "%s", e.what());
+    return SRW_ERR_INVALID;
+  }
+}
+
+int32_t srw_parse_sources(const char *path, int32_t **ids, int64_t *n, char *err, size_t errlen) {
+  if (!path || !ids || !n) return SRW_ERR_INVALID;
+  *ids = nullptr; *n = 0;
+  try {
+    std::vector<int32_t> v;
+    parse_sources_file(path, v);
+    int32_t *out = (int32_t *)malloc(std::max<size_t>(v.size() * 4, 1));
+    if (!out) throw Error(SRW_ERR_NOMEM, "host allocation failed");
+    if (!v.empty()) memcpy(out, v.data(), v.size() * 4);
+    *ids = out; *n = (int64_t)v.size();
     return SRW_OK;
   } catch (const Error &e) {
     if (err && errlen) snprintf(err, errlen, "%s", e.what());

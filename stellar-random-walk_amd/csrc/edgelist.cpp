@@ -286,6 +286,39 @@ void parse_one_file(const char *path, bool weighted, bool partitioned, ParsedLin
 }
 }  // namespace
 
+// The --sources file: vertex ids separated by runs of \s / line ends, each token read by parse_int_token — the rule of an edge list's
+// id column.  A UTF-8 byte order mark at the start is skipped, as for an edge list.  An empty file is an empty list.
+void parse_sources_file(const char *path, std::vector<int32_t> &out) {
+  out.clear();
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) throw Error(SRW_ERR_IO, std::string("Input path does not exist: ") + path + " (" + strerror(errno) + ")");
+  struct stat sb;
+  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close(fd); throw Error(SRW_ERR_IO, std::string("Not a file: ") + path); }
+  const size_t size = (size_t)sb.st_size;
+  if (size == 0) { close(fd); return; }
+  const char *data = (const char *)mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+  close(fd);
+  if (data == MAP_FAILED) throw Error(SRW_ERR_IO, std::string("cannot mmap ") + path);
+  struct Unmap { const char *p; size_t n; ~Unmap() { munmap((void *)p, n); } } unmap{data, size};
+  size_t i = (size >= 3 && (unsigned char)data[0] == 0xEF && (unsigned char)data[1] == 0xBB && (unsigned char)data[2] == 0xBF) ? 3 : 0;
+  int64_t line = 1;
+  while (i < size) {
+    const unsigned char c = (unsigned char)data[i];
+    if (java_ws(c)) {
+      if (c == '\n' || (c == '\r' && !(i + 1 < size && data[i + 1] == '\n'))) ++line;     // \n, \r\n or a lone \r ends a line
+      ++i;
+      continue;
+    }
+    const size_t tb = i;
+    while (i < size && !java_ws((unsigned char)data[i])) ++i;
+    int32_t v;
+    if (!parse_int_token(data + tb, i - tb, v))
+      throw Error(SRW_ERR_PARSE, "line " + std::to_string(line) + ": NumberFormatException for vertex id: For input string: \"" +
+                                     std::string(data + tb, i - tb) + "\"");
+    out.push_back(v);
+  }
+}
+
 // `--input` may name a directory, as with sc.textFile (FileInputFormat): every file in it whose name does not start with
 // '_' or '.' (hiddenFileFilter: _SUCCESS, .crc files) is read, here in byte order of the names (what HDFS lists; the
 // adjacency order — and with it the walk — follows the line order, so it is fixed like this), each with its own byte

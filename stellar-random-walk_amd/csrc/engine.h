@@ -184,6 +184,13 @@ struct srw_handle {
   srw::DevBuf<char> round_state;                 // the table walk in rounds (walk_rounds.hip): 80 B of parked state per walker ...
   srw::DevBuf<int32_t> round_list;               // ... the two work lists (walkers a lane advances | walkers whose next step the wave serves) ...
   srw::DevBuf<unsigned long long> round_ctr;     // ... their lengths and the kernels' cursors
+  // srw_set_sources: the caller's start vertices as the walk kernels read them (ids, or slots on a graph with compacted ids), in
+  // list order.  n_sources < 0: no list — one walker per present vertex and iteration, as ever.
+  srw::DevBuf<int32_t> src_verts, src_ids;       // the list in force | the ids as given (staging of the resolve kernel)
+  srw::DevBuf<unsigned long long> src_bad;       // smallest position of an id that is no vertex of the graph
+  int64_t n_sources = -1;
+  int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
+  const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
   int n_cus = 256;
   int64_t planned_walks = 0;                     // srw_plan_walks: the job's numWalks (0: unknown -> the reference's default 10)
   double shard_prof_acc[4] = {0, 0, 0, 0}, shard_prof_mx[4] = {0, 0, 0, 0};   // SRW_SHARD_PROFILE: per-kernel times of the super-steps (run_shard_superstep)
@@ -254,6 +261,8 @@ struct ParsedLines {
   RawVec<float> w;
 };
 void parse_edgelist_file(const char *path, bool weighted, bool partitioned, ParsedLines &out);
+// --sources file: ids separated by white space / line ends, each read by the edge list's id rule (Integer.parseInt)
+void parse_sources_file(const char *path, std::vector<int32_t> &out);
 
 // ---- writer.cpp (host) ----
 void write_path_files(const int32_t *paths, const int32_t *lens, int64_t n_walkers, int64_t stride,
@@ -279,6 +288,11 @@ class PathWriter {
 // ---- edgelist_device.hip ----
 // Device-side tokenizer for two-column integer edge lists (+ a short decimal weight column); false = not that shape (or any doubt): use the host tokenizer.
 bool load_edgelist_device(srw_handle *h, const char *path, bool directed, bool weighted);
+
+// ---- sources.hip ----
+// The list of start vertices of the next walks: h_ids (host) or d_ids (on the handle's device), n entries.  Throws SRW_ERR_INVALID and
+// leaves the list in force untouched when an id is no vertex of the graph.
+void set_sources(srw_handle *h, const int32_t *h_ids, const void *d_ids, int64_t n);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);

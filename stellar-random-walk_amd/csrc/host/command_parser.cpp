@@ -77,6 +77,7 @@ std::string CommandParser::usage() {
     << "  --gpus <value>           GPUs of this node to shard the graph over (by source vertex; 1 = whole graph on one GPU): 1\n"
     << "  --crc <value>            also write Hadoop .crc side files: false\n"
     << "  --sampler <value>        reference (bit-identical CDF inversion) | alias (alias tables + rejection): reference\n"
+    << "  --sources <value>        file of vertex ids (white space separated) to walk from, in that order, instead of from every vertex (randomwalk, node2vec; --gpus 1): every vertex\n"
     << "  --deviceFormat <value>   format the path text on the GPU (false: on host threads): true\n"
     << "Environment: SRW_W2V_DETERMINISTIC=1 trains word2vec in one wave, sentence after sentence (reproducible vectors; the default "
        "trains one wave per sentence, Hogwild, and two runs differ in their last bits even with the same --seed)\n";
@@ -97,7 +98,7 @@ std::optional<Params> CommandParser::parse(const std::vector<std::string> &args,
     if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); inline_val = true; }
     static const char *known[] = {WALK_LENGTH, NUM_WALKS, P, Q, RDD_PARTITIONS, WEIGHTED, DIRECTED, SINGLE_OUTPUT,
                                   W2V_PARTITIONS, INPUT, OUTPUT, CMD, PARTITIONED, LEARNING_RATE, ITERATION, DIMENSION,
-                                  WINDOW, "seed", "constR", "device", "gpus", "crc", "sampler", "deviceFormat"};
+                                  WINDOW, "seed", "constR", "device", "gpus", "crc", "sampler", "deviceFormat", "sources"};
     if (std::find_if(std::begin(known), std::end(known), [&](const char *k) { return name == k; }) == std::end(known)) {
       fail("Unknown option " + a);
       continue;
@@ -138,6 +139,7 @@ std::optional<Params> CommandParser::parse(const std::vector<std::string> &args,
     else if (name == "gpus") { asInt(c.gpus); if (c.gpus < 1 || c.gpus > 64) fail("Option --gpus must be in 1 .. 64"); }
     else if (name == "crc") asBool(c.crc);
     else if (name == "deviceFormat") asBool(c.deviceFormat);
+    else if (name == "sources") { c.sources = val; c.hasSources = true; }
     else if (name == "sampler") {
       if (val == "alias") c.alias = true; else if (val == "reference") c.alias = false;
       else fail("Option --sampler failed when given '" + val + "' (reference | alias)");
@@ -146,6 +148,9 @@ std::optional<Params> CommandParser::parse(const std::vector<std::string> &args,
   if (!c.hasInput) fail("Missing option --input");    // .required(), CommandParser.scala:64-67
   if (!c.hasOutput) fail("Missing option --output");  // :68-71
   if (!c.hasCmd) fail("Missing option --cmd");        // :72-75
+  // the vertex-sharded walk seeds its walkers the way the vertices are spread over the shards: no list of start vertices there
+  if (c.hasSources && c.gpus > 1) fail("Option --sources needs --gpus 1 (the vertex-sharded walk starts from every vertex)");
+  if (c.hasSources && c.hasCmd && c.cmd == TaskName::embedding) fail("Option --sources applies to --cmd randomwalk and --cmd node2vec");
   if (!ok) {
     e << "Try --help for more information.\n";
     if (err) *err = e.str();

@@ -329,6 +329,15 @@ int main(int argc, char **argv) {
       std::cerr << err << CommandParser::usage();
       return 1;
     }
+    if (params->hasSources) {            // the list of start vertices: read before any GPU work, so that a bad file fails first
+      int32_t *ids = nullptr; int64_t n = 0;
+      char msg[512] = {0};
+      const int32_t rc = srw_parse_sources(params->sources.c_str(), &ids, &n, msg, sizeof msg);
+      if (rc == SRW_ERR_IO) throw std::runtime_error(std::string("org.apache.hadoop.mapred.InvalidInputException: ") + msg);
+      if (rc != SRW_OK) throw std::runtime_error(std::string("java.lang.NumberFormatException: --sources ") + params->sources + ": " + msg);
+      params->sourceIds.assign(ids, ids + n);
+      srw_free(ids);
+    }
     switch (params->cmd) {               // runJob, Main.scala:112-125
       case TaskName::randomwalk:
         doRandomWalk(*params);

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace randomwalk {
 namespace common {
@@ -45,6 +46,9 @@ struct Params {
   int gpus = 1;             // --gpus: > 1 = graph sharded by source vertex over that many GPUs of this node (srw_cluster_*)
   bool crc = false;         // --crc: also write Hadoop .crc side files
   bool alias = false;       // --sampler alias: Mode A (alias tables + rejection) instead of the reference-exact Mode R
+  std::string sources;      // --sources: file of vertex ids to start the walks from (default: every vertex)
+  bool hasSources = false;
+  std::vector<int32_t> sourceIds;   // its ids in file order (main.cpp fills it before any GPU work)
   bool deviceFormat = true;   // --deviceFormat: the GPU formats the path text (SRW_WALK_DEVICE_FORMAT); false = host threads
 };
 

@@ -106,8 +106,15 @@ void VCutRandomWalk::loadGraph() {
   printGraphStats();
 }
 
+int64_t RandomWalk::applySources() {
+  if (!config_.hasSources) return nVertices;
+  check(h_, srw_set_sources(h_, config_.sourceIds.data(), (int64_t)config_.sourceIds.size()), "--sources");
+  return (int64_t)config_.sourceIds.size();
+}
+
 void RandomWalk::executeOnDevice() {
   loadGraph();
+  const int64_t perIter = applySources();
   Phase ph("randomWalk (kernels; the paths stay in HBM)");
   srw_walk_params P{};
   P.p = (float)config_.p; P.q = (float)config_.q;               // .toFloat, :112
@@ -118,13 +125,13 @@ void RandomWalk::executeOnDevice() {
   srw_walk_stats st{};
   check(h_, srw_walk(h_, &P, &st), "randomWalk");
   if (log_) {
-    std::vector<int32_t> lens((size_t)config_.numWalks * (size_t)nVertices);
+    std::vector<int32_t> lens((size_t)config_.numWalks * (size_t)perIter);
     check(h_, srw_fetch_paths(h_, nullptr, lens.data()), "randomWalk");
     const int32_t stride = config_.walkLength + 2;
     for (int it = 0; it < config_.numWalks; ++it) {
       int64_t dead = 0;
-      const int32_t *ln = lens.data() + (size_t)it * nVertices;
-      for (int64_t i = 0; i < nVertices; ++i) dead += (ln[i] >= 2 && ln[i] < stride);
+      const int32_t *ln = lens.data() + (size_t)it * perIter;
+      for (int64_t i = 0; i < perIter; ++i) dead += (ln[i] >= 2 && ln[i] < stride);
       *log_ << "Unfinished Walkers: 0\n";                       // :154
       if (dead) *log_ << "Wrong Transports: 0\n" << "Zero Neighbors: " << dead << "\n";  // :155-160
     }
@@ -143,7 +150,8 @@ Paths RandomWalk::walkImpl(bool useConst, float constR) {
   Phase ph("randomWalk (kernels + path transfer, overlapped)");
   Paths out;
   out.stride = config_.walkLength + 2;
-  out.n = (int64_t)config_.numWalks * nVertices;
+  const int64_t perIter = applySources();
+  out.n = (int64_t)config_.numWalks * perIter;
   if (srw_host_alloc((size_t)out.n * out.stride * 4, (void **)&out.ids) != SRW_OK ||
       srw_host_alloc((size_t)out.n * 4, (void **)&out.lens) != SRW_OK)
     throw std::runtime_error("cannot allocate pinned host memory for the paths");
@@ -160,8 +168,8 @@ Paths RandomWalk::walkImpl(bool useConst, float constR) {
     for (int it = 0; it < config_.numWalks; ++it) {
       // acc2 ("Zero Neighbors", :117): walkers that hit a dead end inside the second-order loop of this iteration
       int64_t dead = 0;
-      const int32_t *ln = out.lens + (size_t)it * nVertices;
-      for (int64_t i = 0; i < nVertices; ++i) dead += (ln[i] >= 2 && ln[i] < out.stride);
+      const int32_t *ln = out.lens + (size_t)it * perIter;
+      for (int64_t i = 0; i < perIter; ++i) dead += (ln[i] >= 2 && ln[i] < out.stride);
       *log_ << "Unfinished Walkers: 0\n";                       // :154 (one super-step per iteration on one GPU)
       if (dead) *log_ << "Wrong Transports: 0\n" << "Zero Neighbors: " << dead << "\n";  // :155-160
     }
@@ -212,6 +220,7 @@ void RandomWalk::executeAndSaveSharded(int partitions, const std::string &output
 void RandomWalk::executeAndSave(int partitions, const std::string &output) {
   if (config_.gpus > 1) { executeAndSaveSharded(partitions, output); return; }
   loadGraph();
+  applySources();
   Phase ph("randomWalk + save (kernel / PCIe / format+write pipelined)");
   srw_walk_params P{};
   P.p = (float)config_.p; P.q = (float)config_.q;

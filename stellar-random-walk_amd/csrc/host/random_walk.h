@@ -94,6 +94,8 @@ class RandomWalk {  // trait RandomWalk
 
  protected:
   Paths walkImpl(bool useConst, float constR);
+  // after loadGraph: hands config.sourceIds (--sources) to the handle; returns the walkers of one iteration (the list's length, or nVertices)
+  int64_t applySources();
   void printGraphStats();
   Params config_;
   srw_handle *h_ = nullptr;

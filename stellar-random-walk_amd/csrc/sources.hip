@@ -1,0 +1,81 @@
+// sources.hip — walks from a caller-supplied list of start vertices (srw_set_sources / srw_set_sources_device).
+//
+// The walk kernels seed walker wi from verts[wi % n_verts] and key every draw by (seed, iteration, source id, step): nothing in them
+// depends on verts being the list of ALL present vertices.  What this file adds is the list itself — the caller's ids, checked
+// against the graph and turned into what the kernels expect to find in verts[] (the id, or the slot on a graph whose ids were
+// compacted at load) — kept on the handle in the caller's order, duplicates included.  launch_walk reads it through
+// srw_handle::start_verts() / walkers_per_iteration().
+#include "engine.h"
+
+namespace srw {
+namespace {
+constexpr int TPB = 256;
+constexpr unsigned long long NO_BAD = ~0ull;
+
+// first index of [a, a + n) whose value is >= key (a ascending)
+__device__ inline int64_t lower_bound_i32(const int32_t *__restrict__ a, int64_t n, int32_t key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One lane per list entry.  ids[i] is a vertex id as the input spelled it; out[i] receives the entry of the handle's vertex list
+// (verts[n_verts], ascending: ids, or slots when orig_id != nullptr) that stands for it.  An id that is no vertex of the graph
+// leaves out[i] = vmin (never read: the call fails) and lowers *bad to (position << 32 | id): the smallest word names the first one.
+__global__ __launch_bounds__(TPB) void k_sources_resolve(const int32_t *__restrict__ ids, int64_t n, const int32_t *__restrict__ verts,
+                                                         int64_t n_verts, const int32_t *__restrict__ orig_id, int64_t n_slots,
+                                                         int32_t vmin, int32_t *__restrict__ out, unsigned long long *bad) {
+  const int64_t i = blockIdx.x * (int64_t)TPB + threadIdx.x;
+  if (i >= n) return;
+  const int32_t id = ids[i];
+  bool ok = true;
+  int32_t v = id;                                      // what the walk kernels know the vertex by
+  if (orig_id) {                                       // compacted ids: slot = rank among the sorted distinct input ids
+    const int64_t s = lower_bound_i32(orig_id, n_slots, id);
+    ok = s < n_slots && orig_id[s] == id;
+    v = (int32_t)((int64_t)vmin + s);
+  }
+  if (ok) {
+    const int64_t k = lower_bound_i32(verts, n_verts, v);
+    ok = k < n_verts && verts[k] == v;
+  }
+  out[i] = ok ? v : vmin;
+  if (!ok) atomicMin(bad, ((unsigned long long)i << 32) | (uint32_t)id);
+}
+}  // namespace
+
+void set_sources(srw_handle *h, const int32_t *h_ids, const void *d_ids, int64_t n) {
+  Graph &g = h->g;
+  if (!g.loaded) throw Error(SRW_ERR_INVALID, "srw_set_sources: no graph loaded");
+  if (h->cfg.world != 1)
+    throw Error(SRW_ERR_INVALID, "srw_set_sources needs a whole-graph handle (world == 1): the vertex-sharded walk starts from every vertex");
+  if (n < 0 || n >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "srw_set_sources: n must be in [0, 2^31)");
+  if (n > 0 && !h_ids && !d_ids) throw Error(SRW_ERR_INVALID, "srw_set_sources: ids is null");
+  if (n == 0) { h->n_sources = 0; return; }             // a valid list: zero walkers
+  hipStream_t st = h->stream;
+  DevBuf<int32_t> out;
+  out.alloc((size_t)n);
+  h->src_ids.ensure((size_t)n);
+  h->src_bad.ensure(1);
+  SRW_HIP(hipMemcpyAsync(h->src_ids.p, h_ids ? (const void *)h_ids : d_ids, (size_t)n * 4, h_ids ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+  SRW_HIP(hipMemsetAsync(h->src_bad.p, 0xFF, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_sources_resolve, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, (const int32_t *)h->src_ids.p, n,
+                     (const int32_t *)g.verts.p, g.n_vertices, g.compact ? (const int32_t *)g.orig_id.p : nullptr, g.n_slots, g.vmin, out.p,
+                     h->src_bad.p);
+  SRW_HIP(hipGetLastError());
+  unsigned long long bad = NO_BAD;
+  SRW_HIP(hipMemcpyAsync(&bad, h->src_bad.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+  SRW_HIP(hipStreamSynchronize(st));
+  if (bad != NO_BAD) {
+    const int32_t id = (int32_t)(uint32_t)bad;
+    throw Error(SRW_ERR_INVALID, "srw_set_sources: id " + std::to_string(id) + " at position " + std::to_string(bad >> 32) +
+                                     " is not a vertex of the loaded graph");
+  }
+  h->src_verts = std::move(out);
+  h->n_sources = n;
+}
+
+}  // namespace srw

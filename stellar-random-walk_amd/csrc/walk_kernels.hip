@@ -2205,7 +2205,10 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
   Graph &g = h->g;
   { const char *e = getenv("SRW_DEBUG_CHAIN_DEG"); g.dbg_chain_deg = e && *e ? atoi(e) : 0; }      // tests: every table step on a long row is a "tie"
   hipStream_t st = h->stream;
-  const int64_t n_walkers = (int64_t)num_walks * g.n_vertices;
+  // the walkers' start vertices: every present vertex, or the caller's list (srw_set_sources) in its order
+  const int32_t *verts = h->start_verts();
+  const int64_t n_verts = h->walkers_per_iteration();
+  const int64_t n_walkers = (int64_t)num_walks * n_verts;
   const bool alias = P.sampler == SRW_SAMPLER_ALIAS;
   bool first_order_compact = false;
   const bool first_order = !alias && (P.p == 1.0f && P.q == 1.0f) && !(P.flags & SRW_WALK_FORCE_GENERAL);
@@ -2219,10 +2222,10 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
     (void)al_bytes;
     const bool nt = (P.flags & SRW_WALK_NT_LOADS) != 0;
     if (nt)
-      hipLaunchKernelGGL(k_walk_alias<true>, dim3((unsigned)blocks), dim3(TPB), 0, st, gv, g.verts.p, g.n_vertices, n_walkers,
+      hipLaunchKernelGGL(k_walk_alias<true>, dim3((unsigned)blocks), dim3(TPB), 0, st, gv, verts, n_verts, n_walkers,
                          P.walk_length, first_walk, P.seed, P.p, P.q, d_paths, d_lens, h->counters.p);
     else
-      hipLaunchKernelGGL(k_walk_alias<false>, dim3((unsigned)blocks), dim3(TPB), 0, st, gv, g.verts.p, g.n_vertices, n_walkers,
+      hipLaunchKernelGGL(k_walk_alias<false>, dim3((unsigned)blocks), dim3(TPB), 0, st, gv, verts, n_verts, n_walkers,
                          P.walk_length, first_walk, P.seed, P.p, P.q, d_paths, d_lens, h->counters.p);
   } else if (first_order) {
     int64_t blocks = (n_walkers + TPB - 1) / TPB;
@@ -2237,8 +2240,8 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
     const bool compact = g.has_cfo && P.rng_mode == SRW_RNG_PHILOX && !(P.flags & SRW_WALK_NO_COMPACT);
     first_order_compact = compact;
 #define SRW_LAUNCH_FO(NTV, MW, CP)                                                                                  \
-  hipLaunchKernelGGL((k_walk_first_order<NTV, MW, CP>), dim3((unsigned)blocks), dim3(TPB), 0, st, gv, g.verts.p,     \
-                     g.n_vertices, n_walkers, P.walk_length, first_walk, rng, d_paths, d_lens, h->counters.p)
+  hipLaunchKernelGGL((k_walk_first_order<NTV, MW, CP>), dim3((unsigned)blocks), dim3(TPB), 0, st, gv, verts,           \
+                     n_verts, n_walkers, P.walk_length, first_walk, rng, d_paths, d_lens, h->counters.p)
     if (compact) {
       const bool ntc = (P.flags & SRW_WALK_NT_LOADS) ? true : (P.flags & SRW_WALK_CACHED_LOADS) ? false
                        : (size_t)g.n_entries * sizeof(CfoEnt) > ((size_t)2 << 30);
@@ -2287,17 +2290,17 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
       const int64_t qb = (n_walkers + TPB - 1) / TPB;
       const uint32_t q1_max_ret = getenv("SRW_Q1_MAX_RET") ? (uint32_t)atoi(getenv("SRW_Q1_MAX_RET")) : 16u;   // more parallel return edges: the whole wave takes the step
       if ((size_t)g.n_entries * sizeof(CfoEnt) > ((size_t)2 << 30))
-        hipLaunchKernelGGL(k_walk_q1<true>, dim3((unsigned)qb), dim3(TPB), 0, st, gv, g.verts.p, g.n_vertices, n_walkers, P.walk_length,
+        hipLaunchKernelGGL(k_walk_q1<true>, dim3((unsigned)qb), dim3(TPB), 0, st, gv, verts, n_verts, n_walkers, P.walk_length,
                            first_walk, rng, P.p, d_paths, d_lens, h->counters.p, h->walk_todo.p, h->walk_cursor.p + 1, q1_max_ret);
       else
-        hipLaunchKernelGGL(k_walk_q1<false>, dim3((unsigned)qb), dim3(TPB), 0, st, gv, g.verts.p, g.n_vertices, n_walkers, P.walk_length,
+        hipLaunchKernelGGL(k_walk_q1<false>, dim3((unsigned)qb), dim3(TPB), 0, st, gv, verts, n_verts, n_walkers, P.walk_length,
                            first_walk, rng, P.p, d_paths, d_lens, h->counters.p, h->walk_todo.p, h->walk_cursor.p + 1, q1_max_ret);
       todo = h->walk_todo.p;
     }
     if (lean) {
       int64_t lb = std::min<int64_t>((n_walkers * 64 + TPB - 1) / TPB, (int64_t)h->n_cus * 16);
       TabArgs ta;
-      ta.g = gv; ta.verts = g.verts.p; ta.n_verts = g.n_vertices; ta.n_walkers = n_walkers; ta.L = P.walk_length; ta.first_walk = first_walk;
+      ta.g = gv; ta.verts = verts; ta.n_verts = n_verts; ta.n_walkers = n_walkers; ta.L = P.walk_length; ta.first_walk = first_walk;
       ta.rng = rng; ta.p = P.p; ta.q = P.q; ta.paths = d_paths; ta.lens = d_lens; ta.ctr = h->counters.p; ta.cursor = h->walk_cursor.p;
       ta.todo = h->walk_todo.p; ta.todo_n = h->walk_cursor.p + 1; ta.tie = tie;
       // SRW_TABLE_GROUPS=1: one walker per 16 lanes (walk_groups.hip) — measured and not kept as the default, profiles/r06_group_kernel.md
@@ -2323,7 +2326,7 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
       todo = h->walk_todo.p;
       resolve_ties();
     }
-    hipLaunchKernelGGL(k_walk_general, dim3((unsigned)blocks), dim3(TPB), 0, st, gv, g.verts.p, g.n_vertices, n_walkers,
+    hipLaunchKernelGGL(k_walk_general, dim3((unsigned)blocks), dim3(TPB), 0, st, gv, verts, n_verts, n_walkers,
                        P.walk_length, first_walk, rng, P.p, P.q, d_paths, d_lens, h->counters.p, h->walk_cursor.p, tune, todo,
                        h->walk_cursor.p + 1, todo_tie, tie_list, tie_out);
   }
@@ -2411,7 +2414,7 @@ void prepare_tables(srw_handle *h, const srw_walk_params &P) {
                                  //  without the hash 771 ms per iteration, ratio 4 with it 711 ms, r04 s112)
   };
   // what the walk itself allocates after the tables: one call's paths and lengths (+ hand-over lists, chain scratch, the build's HBM-scratch bins)
-  size_t reserve = (size_t)P.num_walks * (size_t)h->g.n_vertices * ((size_t)P.walk_length + 3) * 4 + ((size_t)8 << 30);
+  size_t reserve = (size_t)P.num_walks * (size_t)h->walkers_per_iteration() * ((size_t)P.walk_length + 3) * 4 + ((size_t)8 << 30);
   if (reserve > ((size_t)64 << 30)) reserve = (size_t)64 << 30;      // (srw_walk_to_host / _and_save stream one iteration at a time)
   if (const char *r = getenv("SRW_EB_RESERVE_GB"); r && *r) reserve = (size_t)(atof(r) * (double)((size_t)1 << 30));
   h->g.eb_reserve = reserve;
@@ -2578,10 +2581,10 @@ void run_walk(srw_handle *h, const srw_walk_params &P, srw_walk_stats *stats) {
   if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_walk needs a whole-graph handle (world == 1); use srw_shard_*");
   check_params(P);
   hipStream_t st = h->stream;
-  const int64_t n_walkers = (int64_t)P.num_walks * g.n_vertices;
+  const int64_t n_walkers = (int64_t)P.num_walks * h->walkers_per_iteration();
   if (n_walkers >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "more than 2^31 walkers in one call: lower num_walks");
   const int32_t stride = P.walk_length + 2;
-  if (n_walkers == 0) {   // empty graph or num_walks == 0: nothing to walk
+  if (n_walkers == 0) {   // empty graph, empty source list or num_walks == 0: nothing to walk
     h->res.n_walkers = 0; h->res.stride = stride; h->res.valid = true;
     if (stats) { memset(stats, 0, sizeof(*stats)); }
     return;
@@ -2614,8 +2617,8 @@ void run_walk_to_host(srw_handle *h, const srw_walk_params &P, int32_t *paths, i
   if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_walk_to_host needs a whole-graph handle (world == 1)");
   check_params(P);
   hipStream_t st = h->stream;
-  const int64_t nv = g.n_vertices;
-  if (nv >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "too many vertices");
+  const int64_t nv = h->walkers_per_iteration();   // walkers of one iteration: present vertices, or the source list
+  if (nv >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "too many walkers per iteration");
   const int32_t stride = P.walk_length + 2;
   if (nv == 0 || P.num_walks == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return; }
   const double setup_ms = timed_prepare_tables(h, P);
@@ -2664,7 +2667,7 @@ void run_walk_and_save(srw_handle *h, const srw_walk_params &P, const char *outp
   if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_walk_and_save needs a whole-graph handle (world == 1)");
   check_params(P);
   hipStream_t st = h->stream;
-  const int64_t nv = g.n_vertices;
+  const int64_t nv = h->walkers_per_iteration();   // walkers of one iteration: present vertices, or the source list
   const int32_t stride = P.walk_length + 2;
   PathWriter writer(output_dir, n_parts, (int64_t)P.num_walks * nv, write_crc);   // fails first if <output>/path exists
   if (nv == 0 || P.num_walks == 0) { writer.close(); if (stats) memset(stats, 0, sizeof(*stats)); return; }   // empty part-00000 + _SUCCESS
