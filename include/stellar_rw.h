@@ -223,7 +223,8 @@ int32_t srw_walk_and_save(srw_handle *h, const srw_walk_params *params, const ch
  * loaded graph (the message names the first such id and its position), if no graph is loaded, on a sharded
  * handle (world > 1) or while population 1 is selected.  A vertex of the graph is what srw_graph_vertices lists:
  * one that only appears as the destination of a directed edge is a vertex (its walk is the one-entry path).
- * The srw_shard_* / srw_cluster_* family ignores the list. */
+ * The srw_shard_* family ignores the list; a cluster carries one of its own (srw_cluster_set_sources, below): a single shard
+ * can neither check a list (it knows its own vertices only) nor commit it together with the others. */
 int32_t srw_set_sources(srw_handle *h, const int32_t *ids, int64_t n);
 /* The same with the ids already in device memory on the handle's GPU (a tensor of a training loop): copied and
  * checked on the handle's stream — the caller has made sure that the ids are written before the call; one 8-byte
@@ -343,13 +344,33 @@ int32_t srw_cluster_graph_stats(const srw_cluster *c, int64_t *n_vertices, int64
 /* params->num_walks iterations starting at first_walk, `batch` of them per population (0 = automatic); paths stay on
  * their home devices.  stats: n_steps / dead_ends summed over the shards, kernel_ms = wall time of the super-steps. */
 int32_t srw_cluster_walk(srw_cluster *c, const srw_walk_params *params, int32_t batch, srw_walk_stats *stats);
-/* The last walk in canonical order (iteration major, source id ascending): paths [num_walks * nVertices][walk_length + 2]. */
+/* The last walk in canonical order (iteration major, source id ascending): paths [num_walks * nVertices][walk_length + 2]
+ * (after srw_cluster_set_sources: iteration major, then list order, [num_walks * n][walk_length + 2]). */
 int32_t srw_cluster_fetch_paths(srw_cluster *c, int32_t *paths, int32_t *lens);
 /* walk + RandomWalk.save (RandomWalk.scala:234-241) over the cluster: <output_dir>/path/part-* + _SUCCESS.  The job is streamed
  * batch by batch (device memory: one batch of paths per shard, host memory: one slice), so NO walk result stays behind:
  * srw_cluster_fetch_paths after this call fails with "no walk result" — use srw_cluster_walk when the paths are wanted in memory. */
 int32_t srw_cluster_walk_and_save(srw_cluster *c, const srw_walk_params *params, const char *output_dir, int32_t n_parts,
                                   int32_t write_crc, srw_walk_stats *stats);
+/* ---- walks from a list of start vertices on the cluster ---------------------------------------
+ * srw_set_sources for the vertex-sharded walk, with its semantics: ids[n] (host) are vertex ids as the input spelled them, in any
+ * order, duplicates allowed; the list is copied.  Until srw_cluster_clear_sources or the next srw_cluster_load_* /
+ * _generate_rmat, srw_cluster_walk / _fetch_paths / _walk_and_save seed num_walks * n walkers: canonical walker = iteration * n +
+ * position in the list (iteration major, then LIST order), stats.n_walkers = num_walks * n, and every buffer the caller sizes
+ * reads n where it read nVertices.  The path of (iteration, v) is the row the full walk produces for it — for any world, on
+ * repeated device ordinals as on distinct devices —, a duplicate entry repeats its path, n == 0 gives zero walkers and an empty
+ * but complete <output>/path.  Which sampling tables a call builds does not depend on the list.
+ * Every shard keeps the entries whose vertex it owns, in list order, with their positions (one HIP kernel + a stable
+ * compaction per shard); chunk capacities are sized from n and from the list's skew over the ranks, and the overflow retry
+ * stays behind them.  A set or a clear drops a held walk result (srw_cluster_fetch_paths then fails until the next walk).
+ * SRW_ERR_INVALID, with the previous list (or none) left in force on EVERY shard, if an id is no vertex of the loaded graph —
+ * what srw_graph_vertices of a whole-graph handle lists; a destination-only vertex of a directed graph is one — (the message
+ * names the first such id and its position), if no graph is loaded, if c is NULL, n < 0 or n >= 2^31.
+ * The multi-device path has run on virtual shards of one device only. */
+int32_t srw_cluster_set_sources(srw_cluster *c, const int32_t *ids, int64_t n);
+int32_t srw_cluster_clear_sources(srw_cluster *c);
+/* *n = length of the list in force, -1 when there is none (walks start from every vertex). */
+int32_t srw_cluster_sources(const srw_cluster *c, int64_t *n);
 
 /* ---- the embedding stage (`--cmd node2vec` / `--cmd embedding`) ---------------------------------------
  * Replaces Main.configureWord2Vec + Word2Vec.fit + the vector part of saveModelAndFeatures (M/Main.scala:36-44,77-97,113-124):

@@ -93,6 +93,7 @@ EXPORTS = [
     "srw_shard_rows_commit", "srw_shard_rows_release", "srw_device_alloc", "srw_device_free", "srw_cluster_create", "srw_cluster_destroy", "srw_cluster_last_error",
     "srw_cluster_shard", "srw_cluster_load_edgelist", "srw_cluster_load_coo", "srw_cluster_generate_rmat",
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
+    "srw_cluster_set_sources", "srw_cluster_clear_sources", "srw_cluster_sources",
     "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
     "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
@@ -169,6 +170,9 @@ def lib():
     L.srw_cluster_walk.argtypes = [vp, C.POINTER(WalkParams), C.c_int32, C.POINTER(WalkStats)]
     L.srw_cluster_fetch_paths.argtypes = [vp, i32p, i32p]
     L.srw_cluster_walk_and_save.argtypes = [vp, C.POINTER(WalkParams), C.c_char_p, C.c_int32, C.c_int32, C.POINTER(WalkStats)]
+    L.srw_cluster_set_sources.argtypes = [vp, i32p, C.c_int64]
+    L.srw_cluster_clear_sources.argtypes = [vp]
+    L.srw_cluster_sources.argtypes = [vp, i64p]
     L.srw_shard_select.argtypes = [vp, C.c_int32]
     L.srw_w2v_fit.argtypes = [vp, i32p, i32p, C.c_int64, C.c_int64, C.POINTER(W2vParams), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(C.c_int64)]
     L.srw_w2v_fit_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(W2vParams), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(C.c_int64)]
@@ -668,20 +672,55 @@ class Cluster:
         e.rank, e.world = rank, self.world
         return e
 
-    def walk(self, fetch=True, batch=0, **kw):
+    # ---- start vertices (srw_cluster_set_sources) ----
+    def set_sources(self, ids):
+        """Walk from these vertex ids (numpy array or sequence; any order, duplicates allowed) instead of from every vertex, until
+        clear_sources() or the next load: canonical walker = iteration * len(ids) + position.  Each shard keeps what it owns."""
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError("set_sources: vertex ids must be integers (got %s)" % a.dtype)
+        if a.size and (int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1):
+            raise ValueError("set_sources: a vertex id is outside int32")
+        a = np.array(a.reshape(-1), dtype=np.int32)                      # (a copy: the caller may reuse its array)
+        self._ck(lib().srw_cluster_set_sources(self.h, _i32(a) if a.size else None, a.size))
+        self._src_ids = a
+        return self
+
+    def clear_sources(self):
+        self._ck(lib().srw_cluster_clear_sources(self.h))
+        self._src_ids = None
+        return self
+
+    def sources_len(self):
+        """Length of the list in force, None when there is none (walks start from every vertex)."""
+        n = C.c_int64(0)
+        self._ck(lib().srw_cluster_sources(self.h, C.byref(n)))
+        return None if n.value < 0 else n.value
+
+    _with_sources = Engine._with_sources
+
+    def walk(self, fetch=True, batch=0, sources=None, **kw):
+        """srw_cluster_walk (+ srw_cluster_fetch_paths).  sources=ids: from these vertices only, for this call (the previous state
+        is back afterwards)."""
+        if sources is not None:
+            return self._with_sources(sources, lambda: self.walk(fetch=fetch, batch=batch, **kw))
         P = Engine.params(**kw)
         st = WalkStats()
         self._ck(lib().srw_cluster_walk(self.h, C.byref(P), batch, C.byref(st)))
         if not fetch:
             return st.as_dict()
-        nv = self.stats()[0]
+        nv = self.sources_len()                 # walkers per iteration: the list in force, else every vertex
+        if nv is None:
+            nv = self.stats()[0]
         n = P.num_walks * nv
         paths = np.empty((max(n, 1), P.walk_length + 2), dtype=np.int32)
         lens = np.empty(max(n, 1), dtype=np.int32)
         self._ck(lib().srw_cluster_fetch_paths(self.h, _i32(paths), _i32(lens)))
         return paths[:n], lens[:n], st.as_dict()
 
-    def walk_and_save(self, output_dir, n_parts=1, write_crc=False, **kw):
+    def walk_and_save(self, output_dir, n_parts=1, write_crc=False, sources=None, **kw):
+        if sources is not None:
+            return self._with_sources(sources, lambda: self.walk_and_save(output_dir, n_parts=n_parts, write_crc=write_crc, **kw))
         P = Engine.params(**kw)
         st = WalkStats()
         self._ck(lib().srw_cluster_walk_and_save(self.h, C.byref(P), os.fsencode(output_dir), n_parts, int(write_crc), C.byref(st)))

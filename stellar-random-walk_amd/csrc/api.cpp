@@ -176,7 +176,8 @@ static void need_population0(const srw_handle *h, const char *what) {
     throw srw::Error(SRW_ERR_INVALID, std::string(what) + ": population 1 is selected on this handle (srw_shard_select(h, 0) first)");
 }
 
-static void clear_sources(srw_handle *h) { h->n_sources = -1; h->src_verts.release(); }
+// a load: the handle's own list and, on a shard of a cluster, its share of the cluster's
+static void clear_sources(srw_handle *h) { h->n_sources = -1; h->src_verts.release(); srw::shard_clear_sources(h); }
 
 int32_t srw_set_stream(srw_handle *h, void *hip_stream) {
   if (!h) return SRW_ERR_INVALID;
@@ -392,7 +393,7 @@ int32_t srw_set_sources_device(srw_handle *h, const void *d_ids, int64_t n) {
 
 int32_t srw_clear_sources(srw_handle *h) {
   if (!h) return SRW_ERR_INVALID;
-  return guarded(h, [&] { need_population0(h, "srw_clear_sources"); clear_sources(h); });
+  return guarded(h, [&] { need_population0(h, "srw_clear_sources"); h->n_sources = -1; h->src_verts.release(); });   // (a cluster's list on this shard: srw_cluster_clear_sources)
 }
 
 int32_t srw_sources(const srw_handle *h, int64_t *n) {

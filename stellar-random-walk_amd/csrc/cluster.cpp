@@ -36,6 +36,11 @@ struct srw_cluster {
   int32_t walk_length = 0, num_walks = 0;
   bool valid = false;
   int rows_linked = -1;                            // -1: not tried for this graph; 0: some shard could not; 1: every shard linked
+  // srw_cluster_set_sources: length of the list in force (-1: none; every shard holds its share: srw_handle::sh_src_*) and the
+  // chunk slack its walks start at — 1.25 x the skew of the list over the ranks (world * max_r n_r / n), at least 1.25
+  int64_t n_sources = -1;
+  double src_slack = 1.25;
+  void drop_sources() { n_sources = -1; src_slack = 1.25; }     // after a load: the shards have dropped their shares already
   int32_t world() const { return (int32_t)sh.size(); }
 };
 
@@ -199,7 +204,7 @@ int32_t srw_cluster_load_edgelist(srw_cluster *c, const char *path, int32_t dire
                                   int32_t rdd_partitions) {
   if (!c) return SRW_ERR_INVALID;
   return cguard(c, [&] {
-    c->valid = false; c->rows_linked = -1;
+    c->valid = false; c->rows_linked = -1; c->drop_sources();
     if (c->world() == 1) {
       ck(c, 0, srw_load_edgelist(c->sh[0], path, directed, weighted, partitioned, rdd_partitions));
     } else {
@@ -225,7 +230,7 @@ int32_t srw_cluster_load_coo(srw_cluster *c, const int32_t *src, const int32_t *
                              int64_t n_lines, int32_t directed) {
   if (!c) return SRW_ERR_INVALID;
   return cguard(c, [&] {
-    c->valid = false; c->rows_linked = -1;
+    c->valid = false; c->rows_linked = -1; c->drop_sources();
     each(c, [&](int, srw_handle *h) { return srw_load_coo(h, src, dst, w, pid, n_lines, directed); });
     for (auto &v : c->vrank) v.clear();
   });
@@ -233,10 +238,63 @@ int32_t srw_cluster_load_coo(srw_cluster *c, const int32_t *src, const int32_t *
 int32_t srw_cluster_generate_rmat(srw_cluster *c, int32_t scale, int64_t n_edges, uint32_t seed, int32_t weighted, int32_t directed) {
   if (!c) return SRW_ERR_INVALID;
   return cguard(c, [&] {
-    c->valid = false; c->rows_linked = -1;
+    c->valid = false; c->rows_linked = -1; c->drop_sources();
     each(c, [&](int, srw_handle *h) { return srw_generate_rmat(h, scale, n_edges, seed, weighted, directed); });
     for (auto &v : c->vrank) v.clear();
   });
+}
+
+// ---- a list of start vertices (include/stellar_rw.h) ----
+// Every shard resolves the whole list against its own vertices into a pending sublist (shard_resolve_sources, sources.hip: nothing
+// in force is touched) and reports the first owned id that is no vertex; the smallest word over the shards names the first
+// unknown id of the list.  Only a clean list is committed — on every shard, by moves that cannot fail: all or none.
+int32_t srw_cluster_set_sources(srw_cluster *c, const int32_t *ids, int64_t n) {
+  if (!c) return SRW_ERR_INVALID;
+  return cguard(c, [&] {
+    const int32_t world = c->world();
+    if (c->sh.empty() || !c->sh[0]->g.loaded) throw Error(SRW_ERR_INVALID, "srw_cluster_set_sources: no graph loaded");
+    if (n < 0 || n >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "srw_cluster_set_sources: n must be in [0, 2^31)");
+    if (n > 0 && !ids) throw Error(SRW_ERR_INVALID, "srw_cluster_set_sources: ids is null");
+    std::vector<ShardSources> pend((size_t)world);
+    std::vector<unsigned long long> bad((size_t)world, ~0ull);
+    each(c, [&](int r, srw_handle *h) -> int32_t {
+      try {
+        SRW_HIP(hipSetDevice(c->dev[(size_t)r]));
+        if (h->shard_population != 0) throw Error(SRW_ERR_INVALID, "srw_cluster_set_sources: population 1 is selected on this handle");
+        bad[(size_t)r] = shard_resolve_sources(h, ids, n, pend[(size_t)r]);
+        return SRW_OK;
+      } catch (const Error &e) { h->last_error = e.what(); return e.code; }
+      catch (const std::bad_alloc &) { h->last_error = "host allocation failed"; return SRW_ERR_NOMEM; }
+    });
+    const unsigned long long first = *std::min_element(bad.begin(), bad.end());
+    if (first != ~0ull)
+      throw Error(SRW_ERR_INVALID, "srw_cluster_set_sources: id " + std::to_string((int32_t)(uint32_t)first) + " at position " +
+                                       std::to_string(first >> 32) + " is not a vertex of the loaded graph");
+    int64_t total = 0, most = 0;
+    for (const ShardSources &p : pend) { total += p.n_owned; most = std::max(most, p.n_owned); }
+    if (total != n) throw Error(SRW_ERR_INVALID, "srw_cluster_set_sources: the shards disagree about who owns the vertices of the list");
+    for (int r = 0; r < world; ++r) {
+      SRW_HIP(hipSetDevice(c->dev[(size_t)r]));           // (the buffers a shard lets go of are its device's)
+      shard_commit_sources(c->sh[(size_t)r], std::move(pend[(size_t)r]));
+    }
+    c->n_sources = n;
+    // every source on one rank: that rank's seeds need n_r * batch / world records per receive chunk, world x an even list's
+    c->src_slack = n > 0 ? std::max(1.25, 1.25 * (double)world * (double)most / (double)n) : 1.25;
+    c->valid = false;
+  });
+}
+int32_t srw_cluster_clear_sources(srw_cluster *c) {
+  if (!c) return SRW_ERR_INVALID;
+  return cguard(c, [&] {
+    for (int r = 0; r < c->world(); ++r) { SRW_HIP(hipSetDevice(c->dev[(size_t)r])); shard_clear_sources(c->sh[(size_t)r]); }
+    c->drop_sources();
+    c->valid = false;
+  });
+}
+int32_t srw_cluster_sources(const srw_cluster *c, int64_t *n) {
+  if (!c || !n) return SRW_ERR_INVALID;
+  *n = c->n_sources >= 0 ? c->n_sources : -1;
+  return SRW_OK;
 }
 int32_t srw_cluster_graph_stats(const srw_cluster *c, int64_t *n_vertices, int64_t *n_entries) {
   if (!c || c->sh.empty()) return SRW_ERR_INVALID;
@@ -354,7 +412,10 @@ bool run_batch(srw_cluster *c, const srw_walk_params &P, int32_t B, double slack
   return pops[0].overflow;
 }
 
-struct WalkPlan { std::vector<int64_t> n_local; int64_t n_global = 0, stride = 0; int32_t batch = 1; int kind = 1; };
+// n_local[r] / n_global: path rows per iteration on shard r / on all of them — the vertices, or the entries of the list of start
+// vertices in force; pos[r]: where each of shard r's rows stands in an iteration's canonical order (ascending: the global ranks of
+// its vertices, or the list positions of its entries); slack: what the chunk capacities start at
+struct WalkPlan { std::vector<int64_t> n_local; std::vector<const std::vector<int32_t> *> pos; int64_t n_global = 0, stride = 0; int32_t batch = 1; int kind = 1; double slack = 1.25; };
 WalkPlan plan_walk(srw_cluster *c, const srw_walk_params &P0, int32_t batch) {
   const int32_t world = c->world();
   if (P0.num_walks < 0 || P0.walk_length < 0) throw Error(SRW_ERR_INVALID, "bad walk parameters");
@@ -362,20 +423,28 @@ WalkPlan plan_walk(srw_cluster *c, const srw_walk_params &P0, int32_t batch) {
   WalkPlan w;
   w.stride = (int64_t)P0.walk_length + 2;
   w.n_local.assign((size_t)world, 0);
+  w.pos.assign((size_t)world, nullptr);
   for (int r = 0; r < world; ++r) ck(c, r, srw_shard_capacity(c->sh[(size_t)r], &w.n_local[(size_t)r], &w.n_global));
+  const bool listed = c->n_sources >= 0;
+  if (listed) {
+    w.n_global = c->n_sources; w.slack = c->src_slack;
+    for (int r = 0; r < world; ++r) { w.n_local[(size_t)r] = c->sh[(size_t)r]->sh_n_sources; w.pos[(size_t)r] = &c->sh[(size_t)r]->sh_src_pos_host; }
+  }
   w.kind = (P0.p == 1.0f && P0.q == 1.0f && !(P0.flags & SRW_WALK_FORCE_GENERAL)) ? 1 : 2;
   if (w.n_global == 0 || P0.num_walks == 0) return w;
   if (w.kind == 1 && P0.rng_mode == SRW_RNG_PHILOX && c->rows_linked < 0) link_rows(c);
   if (batch <= 0) {   // as many iterations per population as keep a shard's chunk buffers under ~2 GiB
-    const int64_t per_iter = std::max<int64_t>(1, w.n_global / world * 30);      // 24 B of chunk space per resident walker x slack
+    const int64_t per_iter = std::max<int64_t>(1, (int64_t)((double)(w.n_global / world * 30) * (w.slack / 1.25)));      // 24 B of chunk space per resident walker x slack
     batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>(P0.num_walks, ((int64_t)2 << 30) / per_iter));
   }
   w.batch = std::min(batch, std::max(P0.num_walks, 1));
   for (int r = 0; r < world; ++r) {
+    if (listed) continue;
     if (c->vrank[(size_t)r].size() != (size_t)w.n_local[(size_t)r]) {
       c->vrank[(size_t)r].assign((size_t)w.n_local[(size_t)r], 0);
       if (w.n_local[(size_t)r]) ck(c, r, srw_shard_vertex_ranks(c->sh[(size_t)r], c->vrank[(size_t)r].data()));
     }
+    w.pos[(size_t)r] = &c->vrank[(size_t)r];
   }
   return w;
 }
@@ -406,7 +475,7 @@ int32_t srw_cluster_walk(srw_cluster *c, const srw_walk_params *params, int32_t 
       c->lens[(size_t)r].ensure((size_t)std::max<int64_t>(1, (int64_t)P0.num_walks * w.n_local[(size_t)r]));
     }
     const auto t0 = std::chrono::steady_clock::now();
-    double slack = 1.25;
+    double slack = w.slack;
     std::vector<int32_t *> pth((size_t)world), len((size_t)world);
     // A batch of B >= 2 iterations runs as TWO populations of B / 2 and B - B / 2 on two streams per shard (run_populations):
     // identical paths (a population is defined by its iterations), SRW_CLUSTER_POPULATIONS=1 for the single-population form.
@@ -457,17 +526,20 @@ int32_t srw_cluster_fetch_paths(srw_cluster *c, int32_t *paths, int32_t *lens) {
     const int64_t stride = (int64_t)c->walk_length + 2;
     int64_t n_global = 0, nl = 0;
     ck(c, 0, srw_shard_capacity(c->sh[0], &nl, &n_global));
+    const bool listed = c->n_sources >= 0;           // (the list the walk ran with: a set or a clear drops the result)
+    if (listed) n_global = c->n_sources;
     std::vector<int32_t> hp, hl;
     for (int r = 0; r < world; ++r) {
       int64_t n_local = 0, ng = 0;
       ck(c, r, srw_shard_capacity(c->sh[(size_t)r], &n_local, &ng));
+      if (listed) n_local = c->sh[(size_t)r]->sh_n_sources;
       const int64_t rows = (int64_t)c->num_walks * n_local;
       if (rows == 0) continue;
       SRW_HIP(hipSetDevice(c->dev[(size_t)r]));
       hl.resize((size_t)rows);
       SRW_HIP(hipMemcpy(hl.data(), c->lens[(size_t)r].p, (size_t)rows * 4, hipMemcpyDeviceToHost));
       if (paths) { hp.resize((size_t)(rows * stride)); SRW_HIP(hipMemcpy(hp.data(), c->paths[(size_t)r].p, (size_t)(rows * stride) * 4, hipMemcpyDeviceToHost)); }
-      const std::vector<int32_t> &vr = c->vrank[(size_t)r];
+      const std::vector<int32_t> &vr = listed ? c->sh[(size_t)r]->sh_src_pos_host : c->vrank[(size_t)r];
       for (const auto &b : c->batches) {
         const int64_t base = (int64_t)b.it0 * n_local;
         for (int64_t lw = 0; lw < (int64_t)b.n * n_local; ++lw) {
@@ -495,6 +567,7 @@ int32_t srw_cluster_walk_and_save(srw_cluster *c, const srw_walk_params *params,
     const int32_t world = c->world();
     int64_t nv = 0, ne = 0;
     ck(c, 0, srw_graph_stats(c->sh[0], &nv, &ne));
+    if (c->n_sources >= 0) nv = c->n_sources;        // walkers per iteration: the list in force
     PathWriter writer(output_dir, n_parts, (int64_t)P0.num_walks * nv, write_crc != 0);       // fails first if <output>/path exists
     c->valid = false; c->batches.clear();
     const WalkPlan w = plan_walk(c, P0, 0);
@@ -512,7 +585,7 @@ int32_t srw_cluster_walk_and_save(srw_cluster *c, const srw_walk_params *params,
     slice_rows = std::min<int64_t>(slice_rows, w.n_global);
     std::vector<int32_t> sl_paths((size_t)(slice_rows * stride)), sl_lens((size_t)slice_rows);
     std::vector<std::vector<int32_t>> st_paths((size_t)world), st_lens((size_t)world);       // per-shard staging of a slice's rows
-    double walk_ms = 0.0, slack = 1.25;
+    double walk_ms = 0.0, slack = w.slack;
     std::vector<int32_t *> pth((size_t)world), len((size_t)world);
     for (int r = 0; r < world; ++r) { pth[(size_t)r] = c->paths[(size_t)r].p; len[(size_t)r] = c->lens[(size_t)r].p; }
     for (int32_t it0 = 0; it0 < P0.num_walks;) {
@@ -528,7 +601,7 @@ int32_t srw_cluster_walk_and_save(srw_cluster *c, const srw_walk_params *params,
         continue;
       }
       add_stats(tot, bt);
-      // the batch's rows leave in canonical order: iteration by iteration, slice by slice of the global ranks
+      // the batch's rows leave in canonical order: iteration by iteration, slice by slice of the global ranks (of the list positions)
       for (int32_t i = 0; i < B; ++i) {
         for (int64_t g0 = 0; g0 < w.n_global; g0 += slice_rows) {
           const int64_t g1 = std::min<int64_t>(g0 + slice_rows, w.n_global);
@@ -538,7 +611,7 @@ int32_t srw_cluster_walk_and_save(srw_cluster *c, const srw_walk_params *params,
           for (int r = 0; r < world; ++r)
             th.emplace_back([&, r] {
               try {
-                const std::vector<int32_t> &vr = c->vrank[(size_t)r];
+                const std::vector<int32_t> &vr = *w.pos[(size_t)r];
                 const int64_t l0 = std::lower_bound(vr.begin(), vr.end(), (int32_t)g0) - vr.begin();
                 const int64_t l1 = std::lower_bound(vr.begin(), vr.end(), (int32_t)std::min<int64_t>(g1, 0x7FFFFFFF)) - vr.begin();
                 const int64_t n = l1 - l0;

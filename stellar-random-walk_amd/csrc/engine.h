@@ -191,6 +191,15 @@ struct srw_handle {
   int64_t n_sources = -1;
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
+  // srw_cluster_set_sources: the entries of the cluster's list that THIS shard owns, in list order (shard_set_sources, sources.hip):
+  // what the shard kernels read as verts[] and each entry's position in the whole list (ascending; host copy for the way out in
+  // canonical order).  sh_n_sources = n_r < 0: no list — the shard seeds its own vertices.  sh_list_len: the whole list's length.
+  srw::DevBuf<int32_t> sh_src_verts, sh_src_pos;
+  std::vector<int32_t> sh_src_pos_host;
+  int64_t sh_n_sources = -1, sh_list_len = -1;
+  int64_t shard_rows_per_iteration() const { return sh_n_sources >= 0 ? sh_n_sources : g.n_local_vertices; }   // path rows of this shard per iteration
+  int64_t shard_walkers_per_iteration() const { return sh_n_sources >= 0 ? sh_list_len : g.n_vertices; }      // ... of all shards together
+  const int32_t *shard_start_verts() const { return sh_n_sources >= 0 ? sh_src_verts.p : g.verts.p; }
   int n_cus = 256;
   int64_t planned_walks = 0;                     // srw_plan_walks: the job's numWalks (0: unknown -> the reference's default 10)
   double shard_prof_acc[4] = {0, 0, 0, 0}, shard_prof_mx[4] = {0, 0, 0, 0};   // SRW_SHARD_PROFILE: per-kernel times of the super-steps (run_shard_superstep)
@@ -293,6 +302,13 @@ bool load_edgelist_device(srw_handle *h, const char *path, bool directed, bool w
 // The list of start vertices of the next walks: h_ids (host) or d_ids (on the handle's device), n entries.  Throws SRW_ERR_INVALID and
 // leaves the list in force untouched when an id is no vertex of the graph.
 void set_sources(srw_handle *h, const int32_t *h_ids, const void *d_ids, int64_t n);
+// The vertex-sharded form (cluster.cpp): every shard is handed the WHOLE list and keeps the entries it owns.  shard_resolve_sources
+// checks and compacts them into `out` without touching the list in force and returns the smallest (position << 32 | id) word of an
+// owned id that is no vertex of the graph (all ones: none); the cluster commits on every shard once every shard's word is clean.
+struct ShardSources { DevBuf<int32_t> verts, pos; std::vector<int32_t> pos_host; int64_t n_owned = 0, n_list = 0; };
+unsigned long long shard_resolve_sources(srw_handle *h, const int32_t *h_ids, int64_t n, ShardSources &out);
+void shard_commit_sources(srw_handle *h, ShardSources &&s);
+void shard_clear_sources(srw_handle *h);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);

@@ -2794,8 +2794,9 @@ void shard_layout(const srw_handle *h, int32_t batch, double slack, srw_shard_la
   if (batch < 1) throw Error(SRW_ERR_INVALID, "batch must be >= 1");
   if (!(slack >= 1.0)) slack = 1.25;
   // walkers alive at any time <= batch * nVertices, spread over world^2 (sender, receiver) pairs; owner = id mod world
-  // (or the recorded partition) mixes hubs and leaves, so the pairs are even up to sampling noise
-  const double per_pair = (double)batch * (double)h->g.n_vertices / (double)(world * world);
+  // (or the recorded partition) mixes hubs and leaves, so the pairs are even up to sampling noise.  A list of start vertices
+  // (srw_cluster_set_sources) seeds batch * n walkers instead; its skew over the ranks is the cluster's to put into `slack`.
+  const double per_pair = (double)batch * (double)h->shard_walkers_per_iteration() / (double)(world * world);
   const int64_t cap = (int64_t)(per_pair * slack) + 4096;
   if (cap * world >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "shard chunks too large (world * capacity must stay below 2^31 records): lower the batch");
   out->cap_walkers = cap; out->cap_rets = cap;
@@ -2807,7 +2808,7 @@ ShardIO make_io(const srw_handle *h, int32_t batch, const srw_shard_layout &lay,
   ShardIO io;
   io.recv = (const char *)d_recv; io.chunk_bytes = lay.chunk_bytes; io.cap_w = (int32_t)lay.cap_walkers; io.cap_r = (int32_t)lay.cap_rets;
   io.world = h->cfg.world; io.rank = h->cfg.rank; io.batch = batch;
-  io.pt = h->shard_pt.p; io.lens = d_lens; io.n_rows = h->g.n_local_vertices * batch;
+  io.pt = h->shard_pt.p; io.lens = d_lens; io.n_rows = h->shard_rows_per_iteration() * batch;
   return io;
 }
 void check_shard(const srw_handle *h, int32_t batch, const srw_shard_layout &lay) {
@@ -2815,11 +2816,12 @@ void check_shard(const srw_handle *h, int32_t batch, const srw_shard_layout &lay
   if (h->cfg.world > SHARD_MAX_WORLD) throw Error(SRW_ERR_INVALID, "world larger than 64 shards");
   if (batch < 1 || lay.cap_walkers < 1 || lay.cap_rets < 1 || lay.chunk_bytes != 16 + lay.cap_walkers * SW_BYTES + lay.cap_rets * PR_BYTES)
     throw Error(SRW_ERR_INVALID, "bad shard layout");
-  if ((int64_t)batch * h->g.n_local_vertices >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "batch * local vertices must stay below 2^31");
+  if ((int64_t)batch * h->shard_rows_per_iteration() >= ((int64_t)1 << 31)) throw Error(SRW_ERR_INVALID, "batch * local vertices must stay below 2^31");
 }
 }  // namespace
 
-// Seeds this rank's batch * n_local walkers into its receive buffer, path slot 0 and lens; clears the counters.
+// Seeds this rank's batch * n_local walkers (n_local: its vertices, or its share of the cluster's list of start vertices) into its
+// receive buffer, path slot 0 and lens; clears the counters.
 // p = q = 1, Philox draws and linked compact records on every shard (srw_shard_rows_commit): the fused kernel
 static bool shard_fo_linked(const srw_handle *h, const srw_walk_params &P) {
   return h->g.cfo_linked && P.p == 1.0f && P.q == 1.0f && !(P.flags & (SRW_WALK_FORCE_GENERAL | SRW_WALK_NO_COMPACT)) &&
@@ -2831,7 +2833,7 @@ void run_shard_begin(srw_handle *h, const srw_walk_params &P, int32_t batch, con
   check_shard(h, batch, lay);
   Graph &g = h->g;
   hipStream_t st = h->stream;
-  const int64_t n = g.n_local_vertices * batch;
+  const int64_t n = h->shard_rows_per_iteration() * batch;
   h->counters.ensure(1);
   h->shard_flag.ensure(1);
   SRW_HIP(hipMemsetAsync(h->counters.p, 0, sizeof(DevCounters), st));
@@ -2842,7 +2844,7 @@ void run_shard_begin(srw_handle *h, const srw_walk_params &P, int32_t batch, con
   const bool linked = shard_fo_linked(h, P);
   h->shard_cur.ensure((size_t)SH_CUR_DONE + 1);
   SRW_HIP(hipMemsetAsync(h->shard_cur.p, 0, ((size_t)SH_CUR_DONE + 1) * 4, st));
-  hipLaunchKernelGGL(k_sh_seed, dim3(blocks), dim3(TPB), 0, st, g.verts.p, g.n_local_vertices, io, (char *)d_recv, h->shard_pt.p, d_lens, stride,
+  hipLaunchKernelGGL(k_sh_seed, dim3(blocks), dim3(TPB), 0, st, h->shard_start_verts(), h->shard_rows_per_iteration(), io, (char *)d_recv, h->shard_pt.p, d_lens, stride,
                      linked ? (const Row *)g.rows.p : (const Row *)nullptr, g.vmin, h->shard_flag.p);
   SRW_HIP(hipGetLastError());
 }
@@ -2900,7 +2902,7 @@ void run_shard_superstep(srw_handle *h, const srw_walk_params &P, int32_t batch,
     float ms = 0.f; SRW_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1)); acc[slot] += ms; mx[slot] = std::max(mx[slot], (double)ms);
     if (slot == 1 && getenv("SRW_SHARD_PROFILE_STEPS")) fprintf(stderr, "[shard step] rank %d step %d: %.2f ms\n", h->cfg.rank, step, ms);
   };
-  const int64_t n_rows = g.n_local_vertices * batch;
+  const int64_t n_rows = h->shard_rows_per_iteration() * batch;
   if (step > 1) timed(0, [&] { hipLaunchKernelGGL(k_sh_apply, dim3(n_blocks), dim3(TPB), 0, st, io, h->shard_pt.p, d_lens, n_rows, step - 1); });
   if (linked) {      // sampling + bucketing in one pass; no scratch, no per-block counts
     h->shard_cur.ensure((size_t)SH_CUR_DONE + 1);
@@ -3034,7 +3036,7 @@ void run_shard_flush(srw_handle *h, const srw_walk_params &P, int32_t batch, con
                      int32_t *d_paths, int32_t *d_lens, int64_t stride) {
   check_shard(h, batch, lay);
   const ShardIO io = make_io(h, batch, lay, d_recv, d_lens);
-  const int64_t n_rows = h->g.n_local_vertices * batch;
+  const int64_t n_rows = h->shard_rows_per_iteration() * batch;
   hipLaunchKernelGGL(k_sh_apply, dim3(h->n_cus * 4), dim3(TPB), 0, h->stream, io, h->shard_pt.p, d_lens, n_rows, P.walk_length + 1);
   if (n_rows > 0) {      // the staging becomes the caller's [row][L + 2] matrix (-1 beyond each row's length)
     const int64_t tb = std::min<int64_t>((n_rows + 63) / 64, (int64_t)h->n_cus * 16);
@@ -3042,7 +3044,7 @@ void run_shard_flush(srw_handle *h, const srw_walk_params &P, int32_t batch, con
   }
   SRW_HIP(hipGetLastError());
   // compacted ids: the home rank's paths are complete now (one flush per begin); they leave with the ids of the input
-  const int64_t n = h->g.n_local_vertices * batch;
+  const int64_t n = n_rows;
   if (h->g.compact && n > 0) {
     const int64_t nb = std::min<int64_t>((n + TPB / 64 - 1) / (TPB / 64), (int64_t)h->n_cus * 32);
     hipLaunchKernelGGL(k_paths_to_ids, dim3((unsigned)nb), dim3(TPB), 0, h->stream, d_paths, d_lens, n, stride, (const int32_t *)h->g.orig_id.p);
