@@ -108,6 +108,18 @@ int32_t srw_load_edgelist(srw_handle *h, const char *path, int32_t directed, int
  * pid may be NULL.  Replaces the flatMap/reduceByKey stage, UniformRandomWalk.scala:26-41. */
 int32_t srw_load_coo(srw_handle *h, const int32_t *src, const int32_t *dst, const float *w,
                      const int32_t *pid, int64_t n_lines, int32_t directed);
+/* The same lines already in device memory on the handle's GPU (the edge_index of a training loop; no reference counterpart): builds
+ * exactly the graph srw_load_coo builds from the same values with pid == NULL — rows, order, weight bits, srw_graph_stats, compacted
+ * sparse ids, the owner-filtered build of a sharded handle.  d_src / d_dst: n_lines ids each, int32 or int64 by id_type, each pointer
+ * aligned to its element only (the rows of a contiguous [2][n_lines] array are d_src and d_src + n_lines); d_w: n_lines floats or NULL
+ * (1.0f).  The arrays are only read.  The work is ordered on the handle's stream — the caller has made sure that the arrays are
+ * written before the call.  One kernel finds the id range and narrows int64 ids (csrc/coo_ingest.hip); int32 lines with dense ids on
+ * a whole-graph handle are not copied at all.  SRW_ERR_INVALID, with the graph loaded before still loaded: a NULL d_src / d_dst with
+ * n_lines > 0, n_lines < 0, an unknown id_type, a misaligned pointer, an int64 id outside int32 (the message names the first such
+ * line index, its column and the id). */
+enum { SRW_IDS_I32 = 0, SRW_IDS_I64 = 1 };
+int32_t srw_load_coo_device(srw_handle *h, const void *d_src, const void *d_dst, const float *d_w,
+                            int64_t n_lines, int32_t id_type, int32_t directed);
 /* Complete adjacency rows, the GraphMap.addVertex surface (M/algorithm/GraphMap.scala:23-56,83-85):
  * row i is vertex vids[i] with neighbors [offs[i], offs[i+1]); first occurrence of a vertex wins. */
 int32_t srw_load_adjacency(srw_handle *h, const int32_t *vids, const int64_t *offs, int64_t n_rows,

@@ -21,6 +21,7 @@ CFG_OWNER_FROM_PARTITIONS = 1
 CFG_COMPACT_IDS = 2
 CFG_NO_MEMBERSHIP = 4
 CFG_OWNER_HASH_PARTITIONER = 8
+IDS_I32, IDS_I64 = 0, 1          # srw_load_coo_device: element type of the id arrays
 WALK_FORCE_GENERAL = 1
 WALK_NT_LOADS = 2
 WALK_CACHED_LOADS = 4
@@ -85,7 +86,7 @@ STRATEGIES = ("edge_table", "p1", "p2", "w", "p3", "scan", "prefix", "chain", "e
 
 # every symbol include/stellar_rw.h declares
 EXPORTS = [
-    "srw_create", "srw_destroy", "srw_last_error", "srw_set_stream", "srw_plan_walks", "srw_load_edgelist", "srw_load_coo",
+    "srw_create", "srw_destroy", "srw_last_error", "srw_set_stream", "srw_plan_walks", "srw_load_edgelist", "srw_load_coo", "srw_load_coo_device",
     "srw_load_adjacency", "srw_generate_rmat", "srw_graph_stats", "srw_graph_vertices", "srw_graph_neighbors",
     "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
     "srw_shard_capacity", "srw_shard_vertex_ranks", "srw_shard_layout_for", "srw_shard_begin", "srw_shard_superstep",
@@ -121,6 +122,7 @@ def lib():
     L.srw_plan_walks.argtypes = [vp, C.c_int64]
     L.srw_load_edgelist.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.srw_load_coo.argtypes = [vp, i32p, i32p, f32p, i32p, C.c_int64, C.c_int32]
+    L.srw_load_coo_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32]
     L.srw_load_adjacency.argtypes = [vp, i32p, i64p, C.c_int64, i32p, f32p, i32p]
     L.srw_generate_rmat.argtypes = [vp, C.c_int32, C.c_int64, C.c_uint32, C.c_int32, C.c_int32]
     L.srw_graph_stats.argtypes = [vp, i64p, i64p]
@@ -252,6 +254,15 @@ def save_paths(paths, lens, output_dir, n_parts=1, write_crc=False):
         raise SrwError(rc, lib().srw_last_error(None).decode())
 
 
+class _DeviceArray:
+    """int32 words in HBM that the library owns, as the CUDA array interface spells them (what torch.as_tensor wraps without a copy)."""
+
+    def __init__(self, ptr, shape, owner):
+        self.owner = owner               # the Engine stays alive as long as a tensor over its memory does
+        self.__cuda_array_interface__ = {"shape": tuple(int(x) for x in shape), "typestr": "<i4", "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
 class Engine:
     """One handle = one GPU.  Mirrors the life of the reference's SparkContext + GraphMap + RandomWalk object."""
 
@@ -264,7 +275,7 @@ class Engine:
         if rc != OK:
             self.h = None
             raise SrwError(rc, lib().srw_last_error(None).decode())
-        self.rank, self.world = rank, world
+        self.rank, self.world, self.device = rank, world, device
 
     def close(self):
         if getattr(self, "h", None):
@@ -302,7 +313,21 @@ class Engine:
                                          rdd_partitions))
         return self
 
-    def load_coo(self, src, dst, w=None, pid=None, directed=False):
+    def load_coo(self, src, dst=None, w=None, pid=None, directed=False):
+        """The graph from already-parsed lines in file order.  numpy arrays / sequences (src, dst, optional w and pid) go through the
+        host entry point (srw_load_coo).  Objects with data_ptr() and is_cuda (torch tensors) on the handle's device go through
+        srw_load_coo_device, without leaving HBM: src, dst one-dimensional, contiguous, of one length and one dtype (torch.int32 or
+        torch.int64) — or src alone, one contiguous [2, E] tensor (an edge_index); w a tensor of E weights (converted to float32 on
+        the device if need be).  Anything else about such tensors — another dtype, rows that are not contiguous, differing lengths,
+        another device, pid= (partition ids stay a host matter) — is a TypeError before the library is called.  An int64 id
+        outside int32 is SrwError(ERR_INVALID) and leaves the graph loaded before in place.  CPU tensors take the host path."""
+        if hasattr(src, "data_ptr") and hasattr(src, "is_cuda"):
+            host = self._load_coo_tensors(src, dst, w, pid, directed)
+            if host is None:
+                return self
+            src, dst, w = host                                           # CPU tensors: as numpy arrays, below
+        if dst is None:
+            raise TypeError("load_coo: dst is missing (src alone is the [2, E] form of a device tensor)")
         src = np.ascontiguousarray(src, dtype=np.int32)
         dst = np.ascontiguousarray(dst, dtype=np.int32)
         wp = pp = None
@@ -314,6 +339,49 @@ class Engine:
             pp = _i32(pid)
         self._ck(lib().srw_load_coo(self.h, _i32(src), _i32(dst), wp, pp, len(src), int(directed)))
         return self
+
+    def _load_coo_tensors(self, src, dst, w, pid, directed):
+        """load_coo's tensor form.  Device tensors: checks, then srw_load_coo_device -> None.  CPU tensors: -> (src, dst, w) as numpy."""
+        is_t = lambda x: hasattr(x, "data_ptr") and hasattr(x, "is_cuda")      # noqa: E731
+        if dst is None:
+            if src.dim() != 2 or src.shape[0] != 2:
+                raise TypeError("load_coo: one tensor must have shape [2, E] (got %s)" % (tuple(src.shape),))
+            if not src.is_contiguous():
+                raise TypeError("load_coo: the [2, E] tensor must be contiguous")
+            src, dst = src[0], src[1]
+        elif not is_t(dst):
+            raise TypeError("load_coo: src is a tensor, dst is not")
+        if src.dim() != 1 or dst.dim() != 1 or src.shape[0] != dst.shape[0]:
+            raise TypeError("load_coo: src and dst must be one-dimensional and of one length (got %s, %s)" % (tuple(src.shape), tuple(dst.shape)))
+        if not (src.is_contiguous() and dst.is_contiguous()):
+            raise TypeError("load_coo: the rows of ids must be contiguous")
+        if src.dtype != dst.dtype or str(src.dtype) not in ("torch.int32", "torch.int64"):
+            raise TypeError("load_coo: ids must be torch.int32 or torch.int64, src and dst alike (got %s, %s)" % (src.dtype, dst.dtype))
+        if src.is_cuda != dst.is_cuda or (is_t(w) and w.is_cuda != src.is_cuda):
+            raise TypeError("load_coo: the tensors are on different devices")
+        if not src.is_cuda:
+            return src.numpy(), dst.numpy(), (w.numpy() if is_t(w) else w)
+        import torch
+        dev = src.device
+        mine = getattr(self, "device", None)                             # (a Cluster.shard() view does not know its device)
+        if dst.device != dev or (mine is not None and dev.index != mine):
+            raise TypeError("load_coo: the tensors must be on the handle's device (cuda:%s), got %s, %s" % (mine, dev, dst.device))
+        if pid is not None:
+            raise TypeError("load_coo: pid= goes with host arrays (partition ids are not taken from the device)")
+        n = int(src.shape[0])
+        if w is not None:
+            if not is_t(w):
+                w = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32), device=dev)
+            if w.device != dev:
+                raise TypeError("load_coo: w must be on the ids' device (%s), got %s" % (dev, w.device))
+            if w.dim() != 1 or w.shape[0] != n:
+                raise TypeError("load_coo: w must hold one weight per line (%d), got shape %s" % (n, tuple(w.shape)))
+            w = w.to(torch.float32).contiguous()                         # (both return w itself when there is nothing to do)
+        torch.cuda.current_stream(dev).synchronize()                     # the arrays are written before the handle's stream reads them
+        self._ck(lib().srw_load_coo_device(self.h, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                           C.c_void_p(w.data_ptr()) if w is not None else None, n,
+                                           IDS_I64 if str(src.dtype) == "torch.int64" else IDS_I32, int(directed)))
+        return None
 
     def load_adjacency(self, rows):
         """rows: list of (vid, [(dst, w)] or [(dst, pid, w)]) — the GraphMap.addVertex surface."""
@@ -515,6 +583,18 @@ class Engine:
         dp, dl, n, s = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int32(0)
         self._ck(lib().srw_device_paths(self.h, C.byref(dp), C.byref(dl), C.byref(n), C.byref(s)))
         return dp.value, dl.value, n.value, s.value
+
+    def paths_tensor(self):
+        """(paths, lens) of the last walk as torch int32 tensors [n_walkers, stride] and [n_walkers] on the handle's device: VIEWS of the
+        result where srw_walk left it in HBM (the pointers of srw_device_paths; no copy).  They are valid until the next walk or load
+        on this handle, or its close — clone() what has to outlive that.  Zero walkers give empty tensors."""
+        import torch
+        dp, dl, n, stride = self.device_paths()
+        dev = torch.device("cuda", getattr(self, "device", None) or 0)
+        if n == 0:
+            return torch.empty((0, stride), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev)
+        return (torch.as_tensor(_DeviceArray(dp, (n, stride), self), device=dev),
+                torch.as_tensor(_DeviceArray(dl, (n,), self), device=dev))
 
     def write_paths(self, output_dir, n_parts=1, write_crc=False):
         self._ck(lib().srw_write_paths(self.h, os.fsencode(output_dir), n_parts, int(write_crc)))

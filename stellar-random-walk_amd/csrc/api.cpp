@@ -241,6 +241,43 @@ int32_t srw_load_coo(srw_handle *h, const int32_t *src, const int32_t *dst, cons
   });
 }
 
+int32_t srw_load_coo_device(srw_handle *h, const void *d_src, const void *d_dst, const float *d_w, int64_t n_lines,
+                            int32_t id_type, int32_t directed) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_load_coo_device");
+    // everything that can be wrong with the arguments — an id that does not fit int32 included — is found before the handle changes
+    need(n_lines >= 0, "srw_load_coo_device: n_lines < 0");
+    need(id_type == SRW_IDS_I32 || id_type == SRW_IDS_I64, "srw_load_coo_device: unknown id_type");
+    need(n_lines == 0 || (d_src && d_dst), "srw_load_coo_device: d_src/d_dst are null");
+    if (n_lines == 0) {
+      clear_sources(h);
+      load_lines(h, nullptr, nullptr, nullptr, nullptr, 0, directed != 0);      // the empty graph
+      return;
+    }
+    CooIngest in;
+    coo_ingest(h, d_src, d_dst, n_lines, id_type, in);                          // id range (+ narrowed ids); throws on an id outside int32
+    int32_t vmin = in.vmin, vmax = in.vmax;
+    const bool sparse = ids_are_sparse(h, 2 * n_lines, vmin, vmax);
+    if (!sparse) check_id_range(vmin, vmax);       // before any allocation that is proportional to the id range
+    clear_sources(h);                 // a list of start vertices belongs to the graph it was checked against
+    IdMap idmap;
+    if (sparse) {
+      if (id_type == SRW_IDS_I32) {   // compact_ids rewrites its arguments: the caller's arrays are only read, it gets copies
+        in.narrow_src.alloc((size_t)n_lines); in.narrow_dst.alloc((size_t)n_lines);
+        SRW_HIP(hipMemcpyAsync(in.narrow_src.p, d_src, (size_t)n_lines * 4, hipMemcpyDeviceToDevice, h->stream));
+        SRW_HIP(hipMemcpyAsync(in.narrow_dst.p, d_dst, (size_t)n_lines * 4, hipMemcpyDeviceToDevice, h->stream));
+        in.src = in.narrow_src.p; in.dst = in.narrow_dst.p;
+      }
+      compact_ids(h, const_cast<int32_t *>(in.src), const_cast<int32_t *>(in.dst), n_lines, vmin, vmax, idmap);   // (the narrowed copies)
+    }
+    // a whole-graph handle builds from the arrays as they are; a sharded one (world > 1) takes slices of them block by block
+    // (build_graph_blocked through build_graph_from_device_lines: nothing is staged).  The IdMap travels as in load_lines.
+    build_graph_from_device_lines(h, in.src, in.dst, d_w, n_lines, directed != 0, vmin, vmax, nullptr, sparse ? &idmap : nullptr);
+    h->g.part_of.clear();
+  });
+}
+
 int32_t srw_load_adjacency(srw_handle *h, const int32_t *vids, const int64_t *offs, int64_t n_rows, const int32_t *ids,
                            const float *w, const int32_t *pids) {
   if (!h) return SRW_ERR_INVALID;

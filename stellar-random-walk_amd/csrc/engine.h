@@ -355,6 +355,17 @@ void build_row_filters(srw_handle *h);            // word-blocked Bloom filters 
 void build_first_order_tables(srw_handle *h, bool want_exact);
 void build_pq_tables(srw_handle *h, float p, float q);
 
+// ---- coo_ingest.hip ----
+// srw_load_coo_device: one pass over n > 0 ids per column that are already on the handle's device (id_type: SRW_IDS_*), on the
+// handle's stream.  -> the id range and the int32 columns the builders take: the caller's own arrays (int32: nothing is copied) or
+// the narrowed copies held by `out` (int64).  Throws SRW_ERR_INVALID naming the first int64 id outside int32; synchronises the stream.
+struct CooIngest {
+  int32_t vmin = 0, vmax = -1;
+  const int32_t *src = nullptr, *dst = nullptr;
+  DevBuf<int32_t> narrow_src, narrow_dst;
+};
+void coo_ingest(srw_handle *h, const void *d_src, const void *d_dst, int64_t n, int32_t id_type, CooIngest &out);
+
 // ---- alias_tables.hip ----
 void build_alias_tables(srw_handle *h);
 void build_edge_hash(srw_handle *h);
