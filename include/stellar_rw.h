@@ -407,6 +407,34 @@ int32_t srw_w2v_fit(srw_handle *h, const int32_t *paths, const int32_t *lens, in
  * (for the Huffman tree) and the trained vectors cross PCIe. */
 int32_t srw_w2v_fit_device(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride, const srw_w2v_params *params,
                            int32_t **vocab_ids, float **vectors, int64_t *n_vocab);
+/* ---- skip-gram training batches (no reference counterpart: the reference's trainer is MLlib's hierarchical softmax, above) --------
+ * What a negative-sampling loss over someone's own embedding table consumes, built on the device from paths in the layout srw_walk
+ * leaves them (d_paths [n][stride] int32, row r = lens[r] ids then -1; d_lens [n], 1 <= lens[r] <= stride; both NULL = this handle's
+ * last walk result, n and stride then come from it):
+ *   pos [W][context]        every run of `context` consecutive vertices of every path.  Row r has cnt[r] = max(0, lens[r] - context + 1)
+ *                           windows, window (r, j) = paths[r][j .. j + context - 1] is output row off[r] + j, off = exclusive prefix sum
+ *                           of cnt (row-major, then j ascending), W = sum of cnt.  No window holds a -1.
+ *   neg [W][num_negatives]  entry k of window (r, j) = V[(word * nV) >> 32] with
+ *                           word = philox4x32_10(ctr = (r, j, k >> 2, epoch), key = (seed, 1))[k & 3] and V[nV] the present vertices in
+ *                           ascending order (what srw_graph_vertices lists; input ids, also on a graph whose ids were compacted).
+ *                           Uniform over the present vertices and NOT filtered against the window's own vertices (as PyG's
+ *                           Node2Vec.neg_sample).  The key is (row index WITHIN THE CALL, window start, k), never the window's place in
+ *                           the output: a row's negatives do not depend on what else is in the batch, and a call over rows [a, b) of a
+ *                           result (pointer offset, n = b - a) keys row r of the result as r - a.  Key word 1 keeps the stream apart
+ *                           from the walk's (seed, 0); epoch gives fresh negatives for the same rows on the next pass.
+ * d_pos == NULL: count only — *n_windows = W, nothing else is written (one reduction over lens).  Otherwise d_pos[W * context] and, when
+ * num_negatives > 0, d_neg[W * num_negatives] (the caller's buffers, int32, 4-byte aligned) are filled, unless W > cap_windows: then
+ * nothing is written, *n_windows = W and the call fails with SRW_ERR_INVALID (the message names both numbers).  The work runs on the
+ * handle's stream and is complete on return; W (8 bytes) is the only read-back.  Every offset is 64-bit: W * context may exceed 2^31.
+ * SRW_ERR_INVALID before anything is launched: a NULL h / sp / n_windows, no walk result behind NULL pointers (or one pointer alone),
+ * n < 0 or n, stride >= 2^31, context < 1 or > stride, num_negatives < 0, num_negatives > 0 with no graph loaded or (when filling)
+ * without d_neg, a sharded handle (world > 1), population 1 selected.  n == 0 and W == 0 are valid results; context == 1 is valid.
+ * n == 0 with a pointer given is SRW_OK with *n_windows = 0 whatever stride and the other pointer are (an empty tensor's are arbitrary);
+ * two NULL pointers always mean the last walk result, never an empty array. */
+typedef struct { int32_t context; int32_t num_negatives; uint32_t seed; uint32_t epoch; } srw_skipgram_params;
+int32_t srw_skipgram_windows(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride,
+                             const srw_skipgram_params *sp, void *d_pos, void *d_neg, int64_t cap_windows,
+                             int64_t *n_windows);
 /* Unit-test hook (host only, no GPU): word2vec.c's CreateBinaryTree as the trainer uses it.  counts[n_vocab] in descending order ->
  * code_len[n_vocab], codes[n_vocab][40] (bits, root first), points[n_vocab][40] (rows of syn1 on the path, root = n_vocab - 2 first;
  * -1 beyond the code).  Known answers: tests/test_w2v_known_answers.py. */

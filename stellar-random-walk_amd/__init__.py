@@ -48,6 +48,10 @@ def w2v_save(vocab_ids, vectors, output_dir, n_parts=1):
         raise SrwError(rc, "srw_w2v_save: %s" % lib().srw_last_error(None).decode())
 
 
+class SkipgramParams(C.Structure):
+    _fields_ = [("context", C.c_int32), ("num_negatives", C.c_int32), ("seed", C.c_uint32), ("epoch", C.c_uint32)]
+
+
 class SrwError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("srw error %d: %s" % (code, msg))
@@ -95,7 +99,7 @@ EXPORTS = [
     "srw_cluster_shard", "srw_cluster_load_edgelist", "srw_cluster_load_coo", "srw_cluster_generate_rmat",
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
     "srw_cluster_set_sources", "srw_cluster_clear_sources", "srw_cluster_sources",
-    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
+    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
     "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
 
@@ -178,6 +182,7 @@ def lib():
     L.srw_shard_select.argtypes = [vp, C.c_int32]
     L.srw_w2v_fit.argtypes = [vp, i32p, i32p, C.c_int64, C.c_int64, C.POINTER(W2vParams), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(C.c_int64)]
     L.srw_w2v_fit_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(W2vParams), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(C.c_int64)]
+    L.srw_skipgram_windows.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(SkipgramParams), vp, vp, C.c_int64, i64p]
     L.srw_w2v_save_words.argtypes = [C.POINTER(C.c_char_p), f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
     L.srw_w2v_huffman.argtypes = [C.POINTER(C.c_int64), C.c_int64, i32p, C.POINTER(C.c_uint8), i32p]
     L.srw_w2v_save.argtypes = [i32p, f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
@@ -595,6 +600,65 @@ class Engine:
             return torch.empty((0, stride), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev)
         return (torch.as_tensor(_DeviceArray(dp, (n, stride), self), device=dev),
                 torch.as_tensor(_DeviceArray(dl, (n,), self), device=dev))
+
+    # ---- skip-gram training batches (srw_skipgram_windows) ----
+    def skipgram(self, context, num_negatives=0, seed=1, epoch=0, paths=None, lens=None):
+        """(pos, neg): every window of `context` consecutive vertices of every path as a torch int32 tensor [W, context], and
+        num_negatives vertices per window drawn uniformly from the graph's vertices, [W, num_negatives] (None when num_negatives == 0)
+        — both on the handle's device, allocated by torch and owned by the caller (no views of library memory: they survive the
+        next walk).  Order: path row major, then window start ascending; a dead-ended row gives the windows it has, none holds a -1.
+        Negative k of window (r, j) is keyed by (seed, epoch, r, j, k) alone (include/stellar_rw.h), not filtered against the window.
+        paths / lens default to the last walk's result where it lies in HBM; otherwise contiguous int32 tensors [n, stride] / [n] on
+        the handle's device in the layout of paths_tensor() — anything else is a TypeError before the library is called.
+        Sizing: one count-only call (a reduction over lens) gives W, the tensors are allocated exactly, one fill call follows; the
+        alternative — allocating the bound n * (stride - context + 1) and returning [:W] — would pin the bound's memory behind the
+        view, which on a directed graph is many times W."""
+        import torch
+        if (paths is None) != (lens is None):
+            raise TypeError("skipgram: paths and lens go together")
+        pp = pl = None
+        n, stride = 0, 1
+        if paths is not None:
+            is_t = lambda x: hasattr(x, "data_ptr") and hasattr(x, "is_cuda")      # noqa: E731
+            if not (is_t(paths) and is_t(lens)):
+                raise TypeError("skipgram: paths and lens must be torch tensors")
+            # (shape, contiguity and dtype first, the device last — _load_coo_tensors' order: each refusal can be met without a GPU)
+            if paths.dim() != 2 or lens.dim() != 1 or paths.shape[0] != lens.shape[0]:
+                raise TypeError("skipgram: paths must be [n, stride] and lens [n] (got %s, %s)" % (tuple(paths.shape), tuple(lens.shape)))
+            if not (paths.is_contiguous() and lens.is_contiguous()):
+                raise TypeError("skipgram: paths and lens must be contiguous")
+            if str(paths.dtype) != "torch.int32" or str(lens.dtype) != "torch.int32":
+                raise TypeError("skipgram: paths and lens must be torch.int32 (got %s, %s)" % (paths.dtype, lens.dtype))
+            if not (paths.is_cuda and lens.is_cuda):
+                raise TypeError("skipgram: paths and lens must be in device memory (got %s, %s)" % (paths.device, lens.device))
+            mine = getattr(self, "device", None)
+            if lens.device != paths.device or (mine is not None and paths.device.index != mine):
+                raise TypeError("skipgram: the tensors must be on the handle's device (cuda:%s), got %s, %s" % (mine, paths.device, lens.device))
+            n, stride = int(paths.shape[0]), int(paths.shape[1])
+            dev = paths.device
+            if n == 0 or stride == 0:
+                return (torch.empty((0, context), dtype=torch.int32, device=dev),
+                        torch.empty((0, num_negatives), dtype=torch.int32, device=dev) if num_negatives else None)
+            pp, pl = C.c_void_p(paths.data_ptr()), C.c_void_p(lens.data_ptr())
+            torch.cuda.current_stream(dev).synchronize()                 # the paths are written before the handle's stream reads them
+        else:
+            dev = torch.device("cuda", getattr(self, "device", None) or 0)
+        sp = SkipgramParams(int(context), int(num_negatives), int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF)
+        W = C.c_int64(0)
+        self._ck(lib().srw_skipgram_windows(self.h, pp, pl, n, stride, C.byref(sp), None, None, 0, C.byref(W)))
+        pos = torch.empty((W.value, sp.context), dtype=torch.int32, device=dev)
+        neg = torch.empty((W.value, sp.num_negatives), dtype=torch.int32, device=dev) if sp.num_negatives else None
+        if W.value:
+            torch.cuda.current_stream(dev).synchronize()                 # whatever torch last did with this memory is over
+            self._ck(lib().srw_skipgram_windows(self.h, pp, pl, n, stride, C.byref(sp), C.c_void_p(pos.data_ptr()),
+                                                C.c_void_p(neg.data_ptr()) if neg is not None else None, W.value, C.byref(W)))
+        return pos, neg                                                  # (the library call has completed: nothing to wait for)
+
+    def walk_skipgram(self, sources, context, num_negatives=0, sg_seed=1, epoch=0, **walk_kw):
+        """The per-step call of a training loop: walk(fetch=False, sources=sources, **walk_kw), then skipgram(context, num_negatives,
+        seed=sg_seed, epoch=epoch) over the result where it lies.  sources: a sequence or an int32 tensor, as set_sources takes."""
+        self.walk(fetch=False, sources=sources, **walk_kw)
+        return self.skipgram(context, num_negatives, seed=sg_seed, epoch=epoch)
 
     def write_paths(self, output_dir, n_parts=1, write_crc=False):
         self._ck(lib().srw_write_paths(self.h, os.fsencode(output_dir), n_parts, int(write_crc)))

@@ -637,6 +637,35 @@ int32_t srw_w2v_fit_device(srw_handle *h, const void *d_paths, const void *d_len
   });
 }
 
+int32_t srw_skipgram_windows(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride,
+                             const srw_skipgram_params *sp, void *d_pos, void *d_neg, int64_t cap_windows, int64_t *n_windows) {
+  if (!h || !sp || !n_windows) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_skipgram_windows");
+    need(h->cfg.world == 1, "srw_skipgram_windows needs a whole-graph handle (world == 1)");
+    need(sp->context >= 1, "srw_skipgram_windows: context < 1");
+    need(sp->num_negatives >= 0, "srw_skipgram_windows: num_negatives < 0");
+    need(sp->num_negatives == 0 || h->g.loaded, "srw_skipgram_windows: num_negatives > 0 needs a loaded graph (the negatives are its vertices)");
+    const int32_t *dp = (const int32_t *)d_paths, *dl = (const int32_t *)d_lens;
+    if (!dp && !dl) {                       // the handle's own last walk (srw_device_paths)
+      if (!h->res.valid) throw Error(SRW_ERR_INVALID, "srw_skipgram_windows: no walk result on this handle");
+      dp = h->res.paths.p; dl = h->res.lens.p; n = h->res.n_walkers; stride = h->res.stride;
+    }
+    need(n >= 0 && n < ((int64_t)1 << 31), "srw_skipgram_windows: n must be in [0, 2^31)");
+    if (n == 0) { *n_windows = 0; return; }     // a valid result whatever stride and the pointers of an empty array are; nothing to launch
+    need(stride >= 1 && stride < ((int64_t)1 << 31), "srw_skipgram_windows: stride must be in [1, 2^31)");
+    need(sp->context <= stride, "srw_skipgram_windows: context > stride");
+    need(dp && dl, "srw_skipgram_windows: one of d_paths / d_lens is null");
+    need(!d_pos || sp->num_negatives == 0 || d_neg, "srw_skipgram_windows: num_negatives > 0 and d_neg is null");
+    need(((uintptr_t)dp & 3u) == 0 && ((uintptr_t)dl & 3u) == 0 && ((uintptr_t)d_pos & 3u) == 0 && ((uintptr_t)d_neg & 3u) == 0,
+         "srw_skipgram_windows: a pointer is not aligned to int32");
+    const int64_t W = skipgram_windows(h, dp, dl, n, stride, *sp, (int32_t *)d_pos, (int32_t *)d_neg, cap_windows);
+    *n_windows = W;
+    if (d_pos && W > cap_windows)
+      throw Error(SRW_ERR_INVALID, "srw_skipgram_windows: " + std::to_string(W) + " windows do not fit cap_windows = " + std::to_string(cap_windows));
+  });
+}
+
 int32_t srw_w2v_huffman(const int64_t *counts, int64_t n_vocab, int32_t *code_len, uint8_t *codes, int32_t *points) {
   if (!counts || !code_len || !codes || !points || n_vocab < 0) return SRW_ERR_INVALID;
   try { w2v_huffman(counts, n_vocab, code_len, codes, points); return SRW_OK; }

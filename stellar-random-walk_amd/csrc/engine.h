@@ -189,6 +189,8 @@ struct srw_handle {
   srw::DevBuf<int32_t> src_verts, src_ids;       // the list in force | the ids as given (staging of the resolve kernel)
   srw::DevBuf<unsigned long long> src_bad;       // smallest position of an id that is no vertex of the graph
   int64_t n_sources = -1;
+  srw::DevBuf<int64_t> sg_off;                   // srw_skipgram_windows: first window of every row [n + 1] ...
+  srw::DevBuf<char> sg_temp;                     // ... and rocprim's temporary storage (both kept between calls: one call per training step)
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
   // srw_cluster_set_sources: the entries of the cluster's list that THIS shard owns, in list order (shard_set_sources, sources.hip):
@@ -309,6 +311,13 @@ struct ShardSources { DevBuf<int32_t> verts, pos; std::vector<int32_t> pos_host;
 unsigned long long shard_resolve_sources(srw_handle *h, const int32_t *h_ids, int64_t n, ShardSources &out);
 void shard_commit_sources(srw_handle *h, ShardSources &&s);
 void shard_clear_sources(srw_handle *h);
+
+// ---- skipgram.hip ----
+// srw_skipgram_windows behind its argument checks (api.cpp): paths [n][stride] / lens [n] on the handle's device -> W.  d_pos == nullptr:
+// count only.  Otherwise pos (and neg when sp.num_negatives > 0) are filled unless W > cap_windows (nothing is written then; the
+// caller reports it).  On the handle's stream, complete on return.
+int64_t skipgram_windows(srw_handle *h, const int32_t *d_paths, const int32_t *d_lens, int64_t n, int64_t stride,
+                         const srw_skipgram_params &sp, int32_t *d_pos, int32_t *d_neg, int64_t cap_windows);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);
