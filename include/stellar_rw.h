@@ -435,6 +435,45 @@ typedef struct { int32_t context; int32_t num_negatives; uint32_t seed; uint32_t
 int32_t srw_skipgram_windows(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride,
                              const srw_skipgram_params *sp, void *d_pos, void *d_neg, int64_t cap_windows,
                              int64_t *n_windows);
+/* ---- negatives by vertex weight, kept out of their own window (single-GPU handles) ---------------------------------------
+ * V[nV] is the ascending list of present vertices that srw_graph_vertices returns; every weight and count below is indexed by position
+ * in V.  All four entries are SRW_ERR_INVALID on a NULL handle, a sharded handle (world > 1) or while population 1 is selected; they
+ * run on the handle's stream and are complete on return; argument errors come before any launch; every offset is 64-bit.
+ *
+ * Weight table.  d_w: n unsigned 32-bit weights in device memory on the handle's GPU.  cdf[i] = w[0] + ... + w[i] as uint64 and
+ * T = cdf[nV - 1].  SRW_ERR_INVALID, with the previous table left in force: n != nV, T == 0, no graph loaded (or one without a vertex),
+ * a pointer that is not aligned to 4 bytes.  d_w == NULL clears the table (n is ignored): draws are uniform again.  Loading a graph
+ * drops the table. */
+int32_t srw_negative_weights_set(srw_handle *h, const void *d_w, int64_t n);
+/* d_out (device memory) receives nV int64 values: the row length of V[i] — what srw_graph_neighbors reports in *n; 0 for a
+ * destination-only vertex of a directed graph. */
+int32_t srw_graph_degrees_device(srw_handle *h, void *d_out);
+/* d_counts (device memory) receives nV int64 values: how often V[i] occurs in the first lens[r] entries of the rows of d_paths
+ * [n][stride] / d_lens [n] (int32, device memory; both NULL = this handle's last walk result, n and stride then come from it).  A
+ * length above the stride is read as the stride.  An id that is no vertex of the graph (only a caller's own arrays can hold one) is
+ * counted in *n_unknown and nowhere else.  d_counts is overwritten, not accumulated; n == 0 with a pointer given zeroes it.
+ * SRW_ERR_INVALID: no graph loaded, NULL d_counts / n_unknown, no walk result behind NULL pointers (or one pointer alone), n < 0 or
+ * n, stride >= 2^31, stride < 1. */
+int32_t srw_path_vertex_counts(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride, void *d_counts,
+                               int64_t *n_unknown);
+/* srw_skipgram_windows with negatives by the weight table in force and, optionally, none that repeats a vertex of its own window.
+ * Windows, pos, the count-only form (d_pos == NULL), cap_windows and the argument errors are exactly those of srw_skipgram_windows (the
+ * same scan and the same fill kernel write pos).  neg [W][num_negatives]: entry k of window (r, j), attempt a (a = 0 when nothing is
+ * excluded), r the row index within the call and j the window start as above:
+ *   with a table    blk = philox4x32_10(ctr = (r, j, k >> 1, epoch), key = (seed, 2 + 2 a)),
+ *                   u = (uint64(blk[2 (k & 1)]) << 32) | blk[2 (k & 1) + 1],  t = (u * T) >> 64 (the high half of the 128-bit product),
+ *                   i = the smallest index with cdf[i] > t; the negative is V[i] (the input id, also on a graph with compacted ids).
+ *                   A vertex of weight 0 is never drawn.
+ *   without one     V[(word * nV) >> 32], word = philox4x32_10(ctr = (r, j, k >> 2, epoch), key = (seed, 1 + 2 a))[k & 3]: attempt 0 is
+ *                   srw_skipgram_windows' draw.  Odd key words are uniform, even ones weighted; the walk keeps (seed, 0).
+ * exclude_window != 0: a draw equal to any of the `context` vertices of its window is rejected and attempt a + 1 is taken, up to
+ * max_draws attempts (1 .. 16, else SRW_ERR_INVALID; ignored when exclude_window == 0).  If every attempt is rejected,
+ * the last attempt's vertex stands — not an error: a graph whose positive-weight vertices all lie in the window cannot do better.  With no table and
+ * exclude_window == 0 the output is bit-identical to srw_skipgram_windows'. */
+typedef struct { int32_t context; int32_t num_negatives; uint32_t seed; uint32_t epoch; int32_t exclude_window; int32_t max_draws; } srw_skipgram_batch_params;
+int32_t srw_skipgram_batch(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride,
+                           const srw_skipgram_batch_params *bp, void *d_pos, void *d_neg, int64_t cap_windows,
+                           int64_t *n_windows);
 /* Unit-test hook (host only, no GPU): word2vec.c's CreateBinaryTree as the trainer uses it.  counts[n_vocab] in descending order ->
  * code_len[n_vocab], codes[n_vocab][40] (bits, root first), points[n_vocab][40] (rows of syn1 on the path, root = n_vocab - 2 first;
  * -1 beyond the code).  Known answers: tests/test_w2v_known_answers.py. */

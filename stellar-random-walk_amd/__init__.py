@@ -52,6 +52,11 @@ class SkipgramParams(C.Structure):
     _fields_ = [("context", C.c_int32), ("num_negatives", C.c_int32), ("seed", C.c_uint32), ("epoch", C.c_uint32)]
 
 
+class SkipgramBatchParams(C.Structure):
+    _fields_ = [("context", C.c_int32), ("num_negatives", C.c_int32), ("seed", C.c_uint32), ("epoch", C.c_uint32),
+                ("exclude_window", C.c_int32), ("max_draws", C.c_int32)]
+
+
 class SrwError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("srw error %d: %s" % (code, msg))
@@ -99,7 +104,7 @@ EXPORTS = [
     "srw_cluster_shard", "srw_cluster_load_edgelist", "srw_cluster_load_coo", "srw_cluster_generate_rmat",
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
     "srw_cluster_set_sources", "srw_cluster_clear_sources", "srw_cluster_sources",
-    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
+    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_negative_weights_set", "srw_graph_degrees_device", "srw_path_vertex_counts", "srw_skipgram_batch", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
     "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
 
@@ -183,6 +188,10 @@ def lib():
     L.srw_w2v_fit.argtypes = [vp, i32p, i32p, C.c_int64, C.c_int64, C.POINTER(W2vParams), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(C.c_int64)]
     L.srw_w2v_fit_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(W2vParams), C.POINTER(i32p), C.POINTER(f32p), C.POINTER(C.c_int64)]
     L.srw_skipgram_windows.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(SkipgramParams), vp, vp, C.c_int64, i64p]
+    L.srw_negative_weights_set.argtypes = [vp, vp, C.c_int64]
+    L.srw_graph_degrees_device.argtypes = [vp, vp]
+    L.srw_path_vertex_counts.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, i64p]
+    L.srw_skipgram_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(SkipgramBatchParams), vp, vp, C.c_int64, i64p]
     L.srw_w2v_save_words.argtypes = [C.POINTER(C.c_char_p), f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
     L.srw_w2v_huffman.argtypes = [C.POINTER(C.c_int64), C.c_int64, i32p, C.POINTER(C.c_uint8), i32p]
     L.srw_w2v_save.argtypes = [i32p, f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
@@ -659,6 +668,129 @@ class Engine:
         seed=sg_seed, epoch=epoch) over the result where it lies.  sources: a sequence or an int32 tensor, as set_sources takes."""
         self.walk(fetch=False, sources=sources, **walk_kw)
         return self.skipgram(context, num_negatives, seed=sg_seed, epoch=epoch)
+
+    # ---- negatives by vertex weight, kept out of their own window (srw_skipgram_batch; DESIGN 7d) ----
+    def _paths_args(self, what, paths, lens):
+        """skipgram's checks of paths= / lens= -> (pointer to paths, pointer to lens, n, stride, device); the pointers are None for the
+        last walk's result.  TypeError before the library is called."""
+        import torch
+        if (paths is None) != (lens is None):
+            raise TypeError("%s: paths and lens go together" % what)
+        if paths is None:
+            return None, None, 0, 1, torch.device("cuda", getattr(self, "device", None) or 0)
+        is_t = lambda x: hasattr(x, "data_ptr") and hasattr(x, "is_cuda")      # noqa: E731
+        if not (is_t(paths) and is_t(lens)):
+            raise TypeError("%s: paths and lens must be torch tensors" % what)
+        if paths.dim() != 2 or lens.dim() != 1 or paths.shape[0] != lens.shape[0]:
+            raise TypeError("%s: paths must be [n, stride] and lens [n] (got %s, %s)" % (what, tuple(paths.shape), tuple(lens.shape)))
+        if not (paths.is_contiguous() and lens.is_contiguous()):
+            raise TypeError("%s: paths and lens must be contiguous" % what)
+        if str(paths.dtype) != "torch.int32" or str(lens.dtype) != "torch.int32":
+            raise TypeError("%s: paths and lens must be torch.int32 (got %s, %s)" % (what, paths.dtype, lens.dtype))
+        if not (paths.is_cuda and lens.is_cuda):
+            raise TypeError("%s: paths and lens must be in device memory (got %s, %s)" % (what, paths.device, lens.device))
+        mine = getattr(self, "device", None)
+        if lens.device != paths.device or (mine is not None and paths.device.index != mine):
+            raise TypeError("%s: the tensors must be on the handle's device (cuda:%s), got %s, %s" % (what, mine, paths.device, lens.device))
+        return C.c_void_p(paths.data_ptr()), C.c_void_p(lens.data_ptr()), int(paths.shape[0]), int(paths.shape[1]), paths.device
+
+    def degrees_tensor(self):
+        """int64 [nV] on the handle's device: the row length of every present vertex, in the order of vertices() (what neighbors(v)
+        reports; 0 for a destination-only vertex of a directed graph)."""
+        import torch
+        dev = torch.device("cuda", getattr(self, "device", None) or 0)
+        out = torch.empty((self.num_vertices,), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._ck(lib().srw_graph_degrees_device(self.h, C.c_void_p(out.data_ptr())))
+        return out
+
+    def visit_counts(self, paths=None, lens=None):
+        """int64 [nV] on the handle's device: how often every present vertex, in the order of vertices(), occurs in the paths — the last
+        walk's result, or tensors as skipgram takes them (the same checks, TypeError before the library is called).  The corpus's
+        unigram counts.  An id in a caller's tensor that is no vertex of the graph is counted in self.last_unknown_ids only."""
+        import torch
+        pp, pl, n, stride, dev = self._paths_args("visit_counts", paths, lens)
+        out = torch.empty((self.num_vertices,), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        if paths is not None and (n == 0 or stride == 0):                # (an empty tensor's pointer is arbitrary, NULL included)
+            self.last_unknown_ids = 0
+            return out.zero_()
+        unknown = C.c_int64(0)
+        self._ck(lib().srw_path_vertex_counts(self.h, pp, pl, n, stride, C.c_void_p(out.data_ptr()), C.byref(unknown)))
+        self.last_unknown_ids = unknown.value
+        return out
+
+    def set_negative_weights(self, weights):
+        """The weight table of skipgram_batch's negatives: a torch tensor [nV] on the handle's device, indexed like vertices().  Returns
+        the int64 tensor of quantised weights now in force; None clears the table (uniform draws again) and returns None.  An integer
+        dtype is taken exactly (a value below 0 or at or above 2^32: ValueError).  A floating dtype is quantised in float64 as
+        q = floor(w / max(w) * (2^32 - 1)), then q = max(q, 1) wherever w > 0 (negative or non-finite values: ValueError).  A vertex of
+        weight 0 is never drawn; all zero is an error of the library.  The table lasts until the next load.  Recipes:
+            e.set_negative_weights(e.visit_counts().double().pow(0.75))      # word2vec's unigram^0.75 table
+            e.set_negative_weights(e.degrees_tensor().double().pow(0.75))    # the degree variant"""
+        if weights is None:
+            self._ck(lib().srw_negative_weights_set(self.h, None, 0))
+            return None
+        import torch
+        if not (hasattr(weights, "data_ptr") and hasattr(weights, "is_cuda")):
+            raise TypeError("set_negative_weights: weights must be a torch tensor")
+        if weights.dim() != 1:
+            raise TypeError("set_negative_weights: weights must be one-dimensional (got %s)" % (tuple(weights.shape),))
+        if weights.dtype == torch.bool or weights.is_complex():
+            raise TypeError("set_negative_weights: weights must be an integer or floating tensor (got %s)" % weights.dtype)
+        # (the values before the device, skipgram's order: each refusal can be met without a GPU)
+        if weights.is_floating_point():
+            w = weights.double()
+            if w.numel() and (not bool(torch.isfinite(w).all()) or bool((w < 0).any())):
+                raise ValueError("set_negative_weights: a weight is negative or not finite")
+            q = torch.floor(w / w.max() * 4294967295.0) if w.numel() and float(w.max()) > 0 else torch.zeros_like(w)
+            q = torch.where(w > 0, torch.clamp(q, min=1.0), q).to(torch.int64)
+        else:
+            q = weights.to(torch.int64)
+            if q.numel() and (int(q.min()) < 0 or int(q.max()) >= 2**32):
+                raise ValueError("set_negative_weights: an integer weight is below 0 or at or above 2^32")
+        if not weights.is_cuda:
+            raise TypeError("set_negative_weights: weights must be in device memory (got %s)" % weights.device)
+        mine = getattr(self, "device", None)
+        if mine is not None and weights.device.index != mine:
+            raise TypeError("set_negative_weights: the tensor must be on the handle's device (cuda:%s), got %s" % (mine, weights.device))
+        w32 = torch.where(q >= 2**31, q - 2**32, q).to(torch.int32)      # uint32 words in an int32 tensor
+        if not w32.numel():
+            w32 = torch.zeros(1, dtype=torch.int32, device=weights.device)   # (a pointer that is not NULL: n = 0 is refused as a wrong length)
+        torch.cuda.current_stream(weights.device).synchronize()          # the weights are written before the handle's stream reads them
+        self._ck(lib().srw_negative_weights_set(self.h, C.c_void_p(w32.data_ptr()), int(q.numel())))
+        return q
+
+    def skipgram_batch(self, context, num_negatives=0, seed=1, epoch=0, paths=None, lens=None, exclude_window=False, max_draws=8):
+        """skipgram with the negatives drawn by the weight table in force (set_negative_weights; uniform without one) and, with
+        exclude_window, none that repeats a vertex of its own window: a draw that does is redrawn, up to max_draws attempts (1 .. 16);
+        the last attempt's vertex stands if all are rejected.  (pos, neg) as skipgram returns them, with its allocation and
+        synchronisation rules; negative k of window (r, j) is keyed by (seed, epoch, r, j, k, attempt) alone (include/stellar_rw.h).
+        With no table and exclude_window=False the result is skipgram's, bit for bit."""
+        import torch
+        pp, pl, n, stride, dev = self._paths_args("skipgram_batch", paths, lens)
+        if paths is not None:
+            if n == 0 or stride == 0:
+                return (torch.empty((0, context), dtype=torch.int32, device=dev),
+                        torch.empty((0, num_negatives), dtype=torch.int32, device=dev) if num_negatives else None)
+            torch.cuda.current_stream(dev).synchronize()                 # the paths are written before the handle's stream reads them
+        bp = SkipgramBatchParams(int(context), int(num_negatives), int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+                                 1 if exclude_window else 0, int(max_draws))
+        W = C.c_int64(0)
+        self._ck(lib().srw_skipgram_batch(self.h, pp, pl, n, stride, C.byref(bp), None, None, 0, C.byref(W)))
+        pos = torch.empty((W.value, bp.context), dtype=torch.int32, device=dev)
+        neg = torch.empty((W.value, bp.num_negatives), dtype=torch.int32, device=dev) if bp.num_negatives else None
+        if W.value:
+            torch.cuda.current_stream(dev).synchronize()                 # whatever torch last did with this memory is over
+            self._ck(lib().srw_skipgram_batch(self.h, pp, pl, n, stride, C.byref(bp), C.c_void_p(pos.data_ptr()),
+                                              C.c_void_p(neg.data_ptr()) if neg is not None else None, W.value, C.byref(W)))
+        return pos, neg
+
+    def walk_skipgram_batch(self, sources, context, num_negatives=0, sg_seed=1, epoch=0, exclude_window=False, max_draws=8, **walk_kw):
+        """walk(fetch=False, sources=sources, **walk_kw), then skipgram_batch(context, num_negatives, seed=sg_seed, epoch=epoch,
+        exclude_window=exclude_window, max_draws=max_draws) over the result where it lies — walk_skipgram with the weighted draw."""
+        self.walk(fetch=False, sources=sources, **walk_kw)
+        return self.skipgram_batch(context, num_negatives, seed=sg_seed, epoch=epoch, exclude_window=exclude_window, max_draws=max_draws)
 
     def write_paths(self, output_dir, n_parts=1, write_crc=False):
         self._ck(lib().srw_write_paths(self.h, os.fsencode(output_dir), n_parts, int(write_crc)))

@@ -666,6 +666,86 @@ int32_t srw_skipgram_windows(srw_handle *h, const void *d_paths, const void *d_l
   });
 }
 
+// what the entries of negatives.hip share: a whole-graph handle with population 0 selected
+static void need_single_gpu(const srw_handle *h, const char *what) {
+  need_population0(h, what);
+  if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, std::string(what) + " needs a whole-graph handle (world == 1)");
+}
+
+int32_t srw_negative_weights_set(srw_handle *h, const void *d_w, int64_t n) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_single_gpu(h, "srw_negative_weights_set");
+    if (!d_w) { negative_weights_clear(h); return; }
+    need(h->g.loaded && h->g.n_vertices > 0, "srw_negative_weights_set: no graph loaded (or one without a vertex)");
+    if (n != h->g.n_vertices)
+      throw Error(SRW_ERR_INVALID, "srw_negative_weights_set: n = " + std::to_string(n) + " weights for " + std::to_string(h->g.n_vertices) + " vertices");
+    need(((uintptr_t)d_w & 3u) == 0, "srw_negative_weights_set: d_w is not aligned to uint32");
+    negative_weights_set(h, (const uint32_t *)d_w, n);
+  });
+}
+
+int32_t srw_graph_degrees_device(srw_handle *h, void *d_out) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_single_gpu(h, "srw_graph_degrees_device");
+    need(h->g.loaded, "srw_graph_degrees_device: no graph loaded");
+    need(d_out && ((uintptr_t)d_out & 7u) == 0, "srw_graph_degrees_device: d_out is null or not aligned to int64");
+    graph_degrees_device(h, (int64_t *)d_out);
+  });
+}
+
+int32_t srw_path_vertex_counts(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride, void *d_counts,
+                               int64_t *n_unknown) {
+  if (!h || !n_unknown) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_single_gpu(h, "srw_path_vertex_counts");
+    need(h->g.loaded, "srw_path_vertex_counts: no graph loaded");
+    need(d_counts && ((uintptr_t)d_counts & 7u) == 0, "srw_path_vertex_counts: d_counts is null or not aligned to int64");
+    const int32_t *dp = (const int32_t *)d_paths, *dl = (const int32_t *)d_lens;
+    if (!dp && !dl) {                       // the handle's own last walk (srw_device_paths)
+      if (!h->res.valid) throw Error(SRW_ERR_INVALID, "srw_path_vertex_counts: no walk result on this handle");
+      dp = h->res.paths.p; dl = h->res.lens.p; n = h->res.n_walkers; stride = h->res.stride;
+    }
+    need(n >= 0 && n < ((int64_t)1 << 31), "srw_path_vertex_counts: n must be in [0, 2^31)");
+    if (n > 0) {
+      need(stride >= 1 && stride < ((int64_t)1 << 31), "srw_path_vertex_counts: stride must be in [1, 2^31)");
+      need(dp && dl, "srw_path_vertex_counts: one of d_paths / d_lens is null");
+      need(((uintptr_t)dp & 3u) == 0 && ((uintptr_t)dl & 3u) == 0, "srw_path_vertex_counts: a pointer is not aligned to int32");
+    }
+    *n_unknown = path_vertex_counts(h, dp, dl, n, stride, (int64_t *)d_counts);   // (n == 0: the counts are zeroed)
+  });
+}
+
+int32_t srw_skipgram_batch(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride,
+                           const srw_skipgram_batch_params *bp, void *d_pos, void *d_neg, int64_t cap_windows, int64_t *n_windows) {
+  if (!h || !bp || !n_windows) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_single_gpu(h, "srw_skipgram_batch");
+    need(bp->context >= 1, "srw_skipgram_batch: context < 1");
+    need(bp->num_negatives >= 0, "srw_skipgram_batch: num_negatives < 0");
+    need(bp->num_negatives == 0 || h->g.loaded, "srw_skipgram_batch: num_negatives > 0 needs a loaded graph (the negatives are its vertices)");
+    need(bp->exclude_window == 0 || (bp->max_draws >= 1 && bp->max_draws <= 16), "srw_skipgram_batch: exclude_window needs max_draws in [1, 16]");
+    const int32_t *dp = (const int32_t *)d_paths, *dl = (const int32_t *)d_lens;
+    if (!dp && !dl) {                       // the handle's own last walk (srw_device_paths)
+      if (!h->res.valid) throw Error(SRW_ERR_INVALID, "srw_skipgram_batch: no walk result on this handle");
+      dp = h->res.paths.p; dl = h->res.lens.p; n = h->res.n_walkers; stride = h->res.stride;
+    }
+    need(n >= 0 && n < ((int64_t)1 << 31), "srw_skipgram_batch: n must be in [0, 2^31)");
+    if (n == 0) { *n_windows = 0; return; }     // as srw_skipgram_windows: a valid result whatever stride and the pointers of an empty array are
+    need(stride >= 1 && stride < ((int64_t)1 << 31), "srw_skipgram_batch: stride must be in [1, 2^31)");
+    need(bp->context <= stride, "srw_skipgram_batch: context > stride");
+    need(dp && dl, "srw_skipgram_batch: one of d_paths / d_lens is null");
+    need(!d_pos || bp->num_negatives == 0 || d_neg, "srw_skipgram_batch: num_negatives > 0 and d_neg is null");
+    need(((uintptr_t)dp & 3u) == 0 && ((uintptr_t)dl & 3u) == 0 && ((uintptr_t)d_pos & 3u) == 0 && ((uintptr_t)d_neg & 3u) == 0,
+         "srw_skipgram_batch: a pointer is not aligned to int32");
+    const int64_t W = skipgram_batch(h, dp, dl, n, stride, *bp, (int32_t *)d_pos, (int32_t *)d_neg, cap_windows);
+    *n_windows = W;
+    if (d_pos && W > cap_windows)
+      throw Error(SRW_ERR_INVALID, "srw_skipgram_batch: " + std::to_string(W) + " windows do not fit cap_windows = " + std::to_string(cap_windows));
+  });
+}
+
 int32_t srw_w2v_huffman(const int64_t *counts, int64_t n_vocab, int32_t *code_len, uint8_t *codes, int32_t *points) {
   if (!counts || !code_len || !codes || !points || n_vocab < 0) return SRW_ERR_INVALID;
   try { w2v_huffman(counts, n_vocab, code_len, codes, points); return SRW_OK; }

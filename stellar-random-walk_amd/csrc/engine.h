@@ -135,6 +135,10 @@ struct Graph {
   DevBuf<int32_t> orig_id;        // [n_slots] rank -> input id (ascending)
   std::vector<int32_t> h_orig_id; // host mirror (boundary look-ups: srw_graph_neighbors, partitions)
   int32_t id_lo = 0, id_hi = -1;  // smallest / largest id a path can print (text capacity of the formatter)
+  // srw_negative_weights_set (negatives.hip): the weight table of srw_skipgram_batch's negatives over verts[]; a load drops it with the graph
+  DevBuf<uint64_t> neg_cdf;       // [n_vertices] inclusive prefix sums of the weights
+  DevBuf<uint32_t> neg_guide;     // [2^neg_gbits + 1] index selected by the draw b << (64 - neg_gbits); the last entry: by t = T - 1
+  uint64_t neg_total = 0; int32_t neg_gbits = 0; bool has_neg = false;
   std::vector<int32_t> part_of;   // VCut: last pId recorded per dst slot, -1 none (host side; empty if unused)
   GraphView view() const { return GraphView{rows.p, ent.p, sids.p, sperm.p, has_fo ? fo.p : nullptr, (has_cfo || cfo_linked || has_cfo_local) ? cfo.p : nullptr, has_al ? al.p : nullptr, has_al ? rsum.p : nullptr,
                      mrows.p ? mrows.p : rows.p, msids.p ? msids.p : sids.p, (has_pq && pq_unit == 0.0) ? pq.p : nullptr, has_pq ? pq_ok.p : nullptr, (has_ehash && use_ehash) ? ehash.p : nullptr, ehash_mask,
@@ -191,6 +195,7 @@ struct srw_handle {
   int64_t n_sources = -1;
   srw::DevBuf<int64_t> sg_off;                   // srw_skipgram_windows: first window of every row [n + 1] ...
   srw::DevBuf<char> sg_temp;                     // ... and rocprim's temporary storage (both kept between calls: one call per training step)
+  srw::DevBuf<unsigned long long> vc_slots;      // srw_path_vertex_counts: occurrences per slot [n_slots], then the ids that are no vertex [1]
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
   // srw_cluster_set_sources: the entries of the cluster's list that THIS shard owns, in list order (shard_set_sources, sources.hip):
@@ -318,6 +323,19 @@ void shard_clear_sources(srw_handle *h);
 // caller reports it).  On the handle's stream, complete on return.
 int64_t skipgram_windows(srw_handle *h, const int32_t *d_paths, const int32_t *d_lens, int64_t n, int64_t stride,
                          const srw_skipgram_params &sp, int32_t *d_pos, int32_t *d_neg, int64_t cap_windows);
+
+// ---- negatives.hip ----
+// Behind their argument checks (api.cpp), on the handle's stream, complete on return.  negative_weights_set: d_w [n = n_vertices] uint32 on
+// the handle's device -> the table in force; throws SRW_ERR_INVALID and leaves the table in force untouched when every weight is 0.
+void negative_weights_set(srw_handle *h, const uint32_t *d_w, int64_t n);
+void negative_weights_clear(srw_handle *h);
+void graph_degrees_device(srw_handle *h, int64_t *d_out);                       // d_out [n_vertices]: row length of every present vertex
+// d_counts [n_vertices]: occurrences of every present vertex in the first min(lens[r], stride) entries of the rows -> ids that are no vertex
+int64_t path_vertex_counts(srw_handle *h, const int32_t *d_paths, const int32_t *d_lens, int64_t n, int64_t stride, int64_t *d_counts);
+// srw_skipgram_batch: skipgram_windows for the windows and pos, then the negatives by the table in force (uniform without one), redrawn
+// while they hit their own window when bp.exclude_window is set
+int64_t skipgram_batch(srw_handle *h, const int32_t *d_paths, const int32_t *d_lens, int64_t n, int64_t stride,
+                       const srw_skipgram_batch_params &bp, int32_t *d_pos, int32_t *d_neg, int64_t cap_windows);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);
