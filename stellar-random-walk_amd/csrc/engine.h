@@ -185,9 +185,6 @@ struct srw_handle {
   srw::DevBuf<srw::DevCounters> counters;
   srw::DevBuf<unsigned long long> walk_cursor;   // [0] next walker of the persistent kernels, [1] walkers handed over by k_walk_tables
   srw::DevBuf<int32_t> walk_todo;                // their indices
-  srw::DevBuf<char> round_state;                 // the table walk in rounds (walk_rounds.hip): 80 B of parked state per walker ...
-  srw::DevBuf<int32_t> round_list;               // ... the two work lists (walkers a lane advances | walkers whose next step the wave serves) ...
-  srw::DevBuf<unsigned long long> round_ctr;     // ... their lengths and the kernels' cursors
   // srw_set_sources: the caller's start vertices as the walk kernels read them (ids, or slots on a graph with compacted ids), in
   // list order.  n_sources < 0: no list — one walker per present vertex and iteration, as ever.
   srw::DevBuf<int32_t> src_verts, src_ids;       // the list in force | the ids as given (staging of the resolve kernel)
@@ -410,7 +407,7 @@ void build_shard_rev_hash(srw_handle *h);        // return edges of the pairs in
 bool build_local_cfo(srw_handle *h);             // sampler_tables.hip: compact records over the local rows (false: some entry needs an escape)
 void build_rev_table(srw_handle *h);             // return-edge positions (k_walk_q1: p != 1, q == 1)
 
-// ---- walk_kernels.hip ----
+// ---- walk_kernels.hip (run_walk*), shard_kernels.hip (shard_layout, run_shard_*) ----
 void run_walk(srw_handle *h, const srw_walk_params &P, srw_walk_stats *stats);
 void run_walk_to_host(srw_handle *h, const srw_walk_params &P, int32_t *paths, int32_t *lens, srw_walk_stats *stats);
 void run_walk_and_save(srw_handle *h, const srw_walk_params &P, const char *output_dir, int n_parts, bool write_crc,

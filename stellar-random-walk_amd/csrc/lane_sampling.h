@@ -1,8 +1,8 @@
-// lane_sampling.h — the certified samplers of sampling.h for ONE LANE: a walker's step taken sequentially by its lane (walk_lanes.hip,
-// walk_rounds.hip).  Same arithmetic as wave_pick_first / wave_pick_masked / binned_resolve<ABS> under the row certificate ROW_PQ_OK (every
+// lane_sampling.h — the certified samplers of sampling.h for ONE LANE: a walker's step taken sequentially by its lane (walk_lanes.hip).
+// Same arithmetic as wave_pick_first / wave_pick_masked / binned_resolve<ABS> under the row certificate ROW_PQ_OK (every
 // sum of variants exact in any order; the divide-free certain-miss / certain-hit compares), therefore the same picks bit for bit.
 #pragma once
-#include "group_sampling.h"
+#include "sampling.h"
 
 namespace srw {
 namespace lane {
@@ -12,6 +12,39 @@ namespace lane {
 #endif
 constexpr int LNB = SRW_LANE_NB;
 constexpr int32_t LANE_ROW_MAX = 255;                 // whole rows a lane walks itself (two passes): every row with a membership mask
+
+// Four consecutive candidates k .. k + 3 of a row (input order): ids + weights (1.0f on unit-weight graphs, GraphView::ids32).
+// Candidates beyond `last` (the last valid position) come back as (id 0, w 0) with valid = false.
+struct Cand4 { int32_t id[4]; float w[4]; bool valid[4]; };
+__device__ inline void load_cand4(const GraphView &g, int64_t roff, int32_t k, int32_t last, Cand4 &c) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) { c.id[t] = 0; c.w[t] = 0.0f; c.valid[t] = k + t <= last; }
+  if (g.ids32) {
+    const int32_t *p = g.ids32 + roff + k;
+    if (k + 3 <= last) {
+      const U32x4 v = *reinterpret_cast<const U32x4 *>(p);
+      c.id[0] = (int32_t)v.a; c.id[1] = (int32_t)v.b; c.id[2] = (int32_t)v.c; c.id[3] = (int32_t)v.d;
+      c.w[0] = c.w[1] = c.w[2] = c.w[3] = 1.0f;
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) if (c.valid[t]) { c.id[t] = p[t]; c.w[t] = 1.0f; }
+    }
+  } else {
+    const Ent *p = g.ent + roff + k;
+    if (k + 3 <= last) {
+      const U32x4 a = *reinterpret_cast<const U32x4 *>(p), b = *reinterpret_cast<const U32x4 *>(p + 2);
+      c.id[0] = (int32_t)a.a; c.w[0] = __uint_as_float(a.b); c.id[1] = (int32_t)a.c; c.w[1] = __uint_as_float(a.d);
+      c.id[2] = (int32_t)b.a; c.w[2] = __uint_as_float(b.b); c.id[3] = (int32_t)b.c; c.w[3] = __uint_as_float(b.d);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) if (c.valid[t]) { const Ent e = p[t]; c.id[t] = e.id; c.w[t] = e.w; }
+    }
+  }
+}
+
+// The certified compares of binned_resolve (sampling.h): num = exact numerator A'_k, pS = fl(p S).
+__device__ inline bool not_miss(int32_t k, double num, double pS) { return !(num * (1.0 + (double)(k + 8) * 0x1p-51) < pS); }
+__device__ inline bool sure_hit(int32_t k, double num, double pS) { return num * (1.0 - (double)(k + 8) * 0x1p-51) >= pS; }
 
 // A lane's loops are chains of dependent round trips unless the loads of a trip are issued together: candidates are taken NB x 4 at a
 // time (NB 16-byte loads per array in flight), whole small levels at once.
@@ -27,9 +60,9 @@ __device__ inline int32_t lane_scan(const GraphView &g, int64_t roff, int32_t k0
   const double lo = pS * (1.0 - ((double)(k1 + 8) * 0x1p-50 + 0x1p-50));
   int32_t res = -1;
   for (int32_t kb = k0; kb <= k1 && res < 0; kb += 4 * NB) {
-    g16::Cand4 c[NB];
+    Cand4 c[NB];
 #pragma unroll
-    for (int b = 0; b < NB; ++b) g16::load_cand4(g, roff, kb + 4 * b, k1, c[b]);
+    for (int b = 0; b < NB; ++b) load_cand4(g, roff, kb + 4 * b, k1, c[b]);
     uint32_t hb[NB][4];
     if (hub) {
 #pragma unroll
@@ -56,10 +89,10 @@ __device__ inline int32_t lane_scan(const GraphView &g, int64_t roff, int32_t k0
         //  per candidate is merged by the compiler into one with a variable index, and the candidates go through scratch)
         const double a0 = acc + (double)w[0], a1 = a0 + (double)w[1], a2 = a1 + (double)w[2], a3 = a2 + (double)w[3];
         if (!(a3 < lo)) {
-          if (c[b].valid[3] && g16::not_miss(kq + 3, a3, pS)) { res = kq + 3; id_out = c[b].id[3]; hit = g16::sure_hit(kq + 3, a3, pS); }
-          if (c[b].valid[2] && g16::not_miss(kq + 2, a2, pS)) { res = kq + 2; id_out = c[b].id[2]; hit = g16::sure_hit(kq + 2, a2, pS); }
-          if (c[b].valid[1] && g16::not_miss(kq + 1, a1, pS)) { res = kq + 1; id_out = c[b].id[1]; hit = g16::sure_hit(kq + 1, a1, pS); }
-          if (c[b].valid[0] && g16::not_miss(kq + 0, a0, pS)) { res = kq + 0; id_out = c[b].id[0]; hit = g16::sure_hit(kq + 0, a0, pS); }
+          if (c[b].valid[3] && not_miss(kq + 3, a3, pS)) { res = kq + 3; id_out = c[b].id[3]; hit = sure_hit(kq + 3, a3, pS); }
+          if (c[b].valid[2] && not_miss(kq + 2, a2, pS)) { res = kq + 2; id_out = c[b].id[2]; hit = sure_hit(kq + 2, a2, pS); }
+          if (c[b].valid[1] && not_miss(kq + 1, a1, pS)) { res = kq + 1; id_out = c[b].id[1]; hit = sure_hit(kq + 1, a1, pS); }
+          if (c[b].valid[0] && not_miss(kq + 0, a0, pS)) { res = kq + 0; id_out = c[b].id[0]; hit = sure_hit(kq + 0, a0, pS); }
         }
         acc = a3;
       }
@@ -82,9 +115,9 @@ __device__ inline int32_t lane_pick_row(const GraphView &g, const Row &r, bool s
   if (!second && g.ids32) S = (double)r.deg;         // unit weights: nothing to read
   else {
     for (int32_t kb = 0; kb < r.deg; kb += 4 * LNB) {
-      g16::Cand4 c[LNB];
+      Cand4 c[LNB];
 #pragma unroll
-      for (int b = 0; b < LNB; ++b) g16::load_cand4(g, r.off, kb + 4 * b, r.deg - 1, c[b]);
+      for (int b = 0; b < LNB; ++b) load_cand4(g, r.off, kb + 4 * b, r.deg - 1, c[b]);
 #pragma unroll
       for (int b = 0; b < LNB; ++b) {
         const int32_t kq = kb + 4 * b;
@@ -186,8 +219,8 @@ __device__ inline int32_t lane_pick_table(const GraphView &g, const Row &rc, int
             if (au + d0 + d1 < thr) { au += d0 + d1; continue; }
             const uint32_t a0 = au + d0, a1 = a0 + d1;
             const double v0 = prev_val + (double)a0 * unit, v1 = prev_val + (double)a1 * unit, vb = prev_val + (double)au * unit;
-            if (g16::not_miss(chunk_end(i_first + e), v0, pS)) { found = e; b_this = v0; b_prev = vb; }
-            else if (e + 1 < n_here && g16::not_miss(chunk_end(i_first + e + 1), v1, pS)) { found = e + 1; b_this = v1; b_prev = v0; }
+            if (not_miss(chunk_end(i_first + e), v0, pS)) { found = e; b_this = v0; b_prev = vb; }
+            else if (e + 1 < n_here && not_miss(chunk_end(i_first + e + 1), v1, pS)) { found = e + 1; b_this = v1; b_prev = v0; }
             au = a1;
           }
         }
@@ -199,7 +232,7 @@ __device__ inline int32_t lane_pick_table(const GraphView &g, const Row &rc, int
       auto elem_miss = [&](int32_t i, double v) {
         const int64_t je = (((int64_t)(i_first + i) + 1) << (6 * L)) - 1;      // the chunk this element is the prefix of
         const int32_t j = (int32_t)(je < n_bins ? je : n_bins - 1);
-        return !g16::not_miss(chunk_end(j), v, pS);
+        return !not_miss(chunk_end(j), v, pS);
       };
       int32_t lo_i = 0, hi_i = n_here;               // first element that is not a certain miss
       double v_lo = prev_val, v_hi = 0.0;            // value just before lo_i, value at hi_i

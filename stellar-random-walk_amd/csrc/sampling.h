@@ -336,7 +336,7 @@ __device__ inline void edge_exists_n(const uint64_t *tab, uint64_t mask, uint32_
 // rounding distance of a CDF boundary and only the exact chain can decide — the caller hands the step to a kernel that has it.
 constexpr int32_t CHAIN_NEEDED = -2;
 
-// ---- the chain, in pieces (shared by wave_chain_pick and the sharded walk's chain kernels, walk_kernels.hip) ------------
+// ---- the chain, in pieces (shared by wave_chain_pick and the chain kernels, chain_kernels.hip) ------------
 // One group of up to 64 quotients d (lane l holds element l, lanes >= cnt ignored) appended to the accumulator: the lane of
 // the first element with acc >= p, or -1 (acc then holds the accumulator after the group).
 __device__ inline int chain_group64(double &acc, double d, int cnt, double p) {
@@ -900,9 +900,6 @@ __device__ inline int32_t wave_pick_returns(const GraphView &g, const Row &rc, c
 //       LDS, four per lane in lockstep; whichever list ends first in id order advances.  At most
 //       |N(curr)| / 256 + |N(prev)| / 1024 rounds, independent of the id range.  (Tried before it: an id-window bitmap
 //       — 6 us per window, 300 windows per step at RMAT-24 — and an LDS hash set per chunk — 3x the LDS operations.)
-#ifndef SRW_W_MATCH_LOOP
-#define SRW_W_MATCH_LOOP 1                    // sorted-chunk intersection: the matches of a lane in a uniform loop (0: four exec-masked blocks, as before round 5)
-#endif
 constexpr int BIN_CAP = 512;                  // f64 bins: 4 KB of the wave's LDS
 constexpr int WIN_WORDS = 1280;               // scratch behind the bins: 5 KB (W stages 1024 sorted ids of N(prev) here)
 constexpr int HCHUNK = 1024;                // ids of N(prev) staged in LDS per round
@@ -1259,9 +1256,9 @@ __device__ inline void binned_fill(const GraphView &g, const Row &rc, const Bias
             for (int j = 0; j < 4; ++j) if (probe[j] < AI[j]) pos[j] += step;
           }
           SRW_U1(tm, t_pass1);
-#if SRW_W_MATCH_LOOP
           // the matches of a lane's four candidates, one per pass of a wave-uniform loop: with ~10 % of the candidates matching, the
           // fullest lane holds two of them, so two passes of the correction code run instead of four exec-masked copies of it
+          // (-3.4 % of the table build against the four blocks, profiles/r05_table_build.md)
           {
             uint32_t hit[4];
 #pragma unroll
@@ -1280,14 +1277,6 @@ __device__ inline void binned_fill(const GraphView &g, const Row &rc, const Bias
               }
             }
           }
-#else
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (want[j] && bch[pos[j]] == AI[j]) {
-              atomicAdd(&bins[AC[j] >> csh], (double)AW[j] - (double)div_exact(AW[j], q_));
-              if (mbits) atomicOr(&mbits[AC[j] >> 5], 1u << (AC[j] & 31));
-            }
-#endif
           // advance the list that ends first
           const int32_t na = (deg - pa) < 256 ? (deg - pa) : 256;
           const int jl = (na - 1) & 3;
@@ -1396,21 +1385,6 @@ __device__ inline int32_t binned_resolve(const GraphView &g, const Row &rc, cons
   auto chunk_end = [&](int32_t j) { const int64_t e = (((int64_t)j + 1) << csh) - 1; return (int32_t)(e < deg ? e : deg - 1); };
   // tables of rows whose every sum is binary32-exact are stored as floats (edge_tables.hip); LDS bins are always f64
   const bool f32t = ABS && g.ebp.f32 && (rflags & ROW_PQ_F32);
-  // A short N(prev) is staged in LDS and searched there by the located chunk's candidates.  On a table step the copy is started
-  // NOW, with direct-to-LDS loads (global_load_lds: no registers, no wait here), so that it travels together with the table's
-  // first block instead of costing a dependent round trip once the chunk is known.  (Speculative: a chunk that turns out to hold
-  // no special does not need it.)
-  bool pre_staged = false;
-#ifdef SRW_PRESTAGE            // measured and not kept (profiles/r04_table_kernel.md): the speculative copy costs requests when the chunk holds no special, -5 %
-  if (ABS && !cmask && stage && !hubbits && m > 0 && m <= 1024) {
-    int P2 = 1; while (P2 < m) P2 <<= 1;
-    for (int32_t t0 = 0; t0 < m; t0 += 64)
-      if (t0 + lane < m)
-        __builtin_amdgcn_global_load_lds(B + t0 + lane, (__attribute__((address_space(3))) void *)(stage + t0), 4, 0, 0);
-    for (int32_t t = m + lane; t < P2; t += 64) stage[t] = 0xFFFFFFFFu;
-    pre_staged = true;
-  }
-#endif
   const double p = (double)r;
   // Certified compares without a divide.  The reference's acc_k = sum of fl(w'_i / S) differs from num / S (num exact)
   // by at most (k + 2) u num / S.  With t = (k + 8) 2^-51 = 4 (k + 8) u:
@@ -1428,25 +1402,18 @@ __device__ inline int32_t binned_resolve(const GraphView &g, const Row &rc, cons
     // S is the last element of the top level
     const bool u16t = eb_pair_u16(rflags, csh, g.ebp);
     const double unit = u16t ? eb_row_unit(rflags) : 0.0;
-#ifndef SRW_LAYOUT_ON_SALU         // (the layout on the vector unit — the offsets only feed per-lane addresses: 577 against 591 ms at config 3, profiles/r04_table_kernel_ab_runs.txt)
+    // (the layout on the vector unit — the offsets only feed per-lane addresses: 577 against 591 ms at config 3, profiles/r04_table_kernel_ab_runs.txt)
     EbLayout lay = eb_layout(f32t, on_vector(n_bins), false, 0, u16t);
     lay.n1 = uni(lay.n1); lay.n2 = uni(lay.n2);
-#else
-    const EbLayout lay = eb_layout(f32t, n_bins, false, 0, u16t);
-#endif
     const int nlev = lay.n2 ? 3 : lay.n1 ? 2 : 1;
     int32_t blk = 0;
     double prev_val = 0.0;                            // prefix just before the block being searched
     jc = 0;
     // (three copies with L a constant: what selects the level's offset / length / shift by L disappears — scalar instructions, the busier
     //  unit: 591 against 604 ms at config 3, profiles/r04_table_kernel_ab_runs.txt)
-#ifdef SRW_EB_ROLLED_LEVELS
-    for (int L = nlev - 1; L >= 0; --L) {
-#else
 #pragma unroll
     for (int L = 2; L >= 0; --L) {
       if (L >= nlev) continue;
-#endif
       const uint32_t off = L == 2 ? lay.l2_off : L == 1 ? lay.l1_off : lay.l0_off;
       const int32_t cnt = L == 2 ? lay.n2 : L == 1 ? lay.n1 : n_bins;
       const int32_t i = blk * 64 + lane;
@@ -1505,9 +1472,7 @@ __device__ inline int32_t binned_resolve(const GraphView &g, const Row &rc, cons
   }
   // candidate-by-candidate evaluation of chunk jc, 256 candidates per round
   const int32_t k0 = (int32_t)((int64_t)jc << csh), k1 = chunk_end(jc);
-  // The entries (and mask words) of a round are requested one round AHEAD: the first round's together with the reads of PQ below,
-  // round r + 1's before round r's probes are waited for — a located chunk of several rounds (hub rows: deg / cap candidates) costs
-  // one dependent round trip per round instead of two.
+  // The entries (and mask words) of the first round are requested together with the reads of PQ below.
   Ent e_nx[PL]; unsigned long long mw_nx[PL];
   auto fetch_round = [&](int32_t base) {
 #pragma unroll
@@ -1537,13 +1502,14 @@ __device__ inline int32_t binned_resolve(const GraphView &g, const Row &rc, cons
   const BiasDiv bdiv(p_, q_);
   const bool one_sign = (q_ > 1.0f && p_ <= q_) || (q_ < 1.0f && p_ >= q_);
   const bool no_specials = one_sign && !cmask && chunk_corr == 0.0;
-  // a short N(prev): staged in LDS once (sorted, padded to a power of two), searched there
+  // a short N(prev): staged in LDS once (sorted, padded to a power of two), searched there — once the chunk is known (a speculative
+  // copy by direct-to-LDS loads at the start of the step costs requests when the chunk holds no special: measured at -5 %,
+  // profiles/r04_table_kernel.md)
   int stage_levels = 0;
   if (!no_specials && !cmask && stage && !hubbits && m > 0 && m <= 1024) {
     stage_levels = m > 1 ? 32 - __builtin_clz((unsigned)(m - 1)) : 0;       // ceil(log2 m): the padded length is a power of two
     const int P2 = 1 << stage_levels;
-    if (pre_staged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the copy started before the table search has landed
-    else for (int32_t t = lane; t < P2; t += 64) stage[t] = t < m ? B[t] : 0xFFFFFFFFu;
+    for (int32_t t = lane; t < P2; t += 64) stage[t] = t < m ? B[t] : 0xFFFFFFFFu;
     if (stage_levels == 0) stage_levels = -1;               // m == 1: one compare, no search level
     __builtin_amdgcn_wave_barrier();
   }
@@ -1569,9 +1535,9 @@ __device__ inline int32_t binned_resolve(const GraphView &g, const Row &rc, cons
 #ifdef SRW_PHASE_TIMING
     tm.t_fin += 1;                                              // rounds of 64 * PL candidates
 #endif
-#ifndef SRW_PREFETCH_ROUNDS
+    // (a round is requested when it is needed: requested one round ahead it is wasted when the answer is in the current one,
+    //  measured at -9 %, profiles/r04_table_kernel.md)
     if (base > k0) fetch_round(base);
-#endif
     Ent e[PL]; bool valid[PL], in[PL], want[PL]; uint32_t xs[PL]; unsigned long long mwc[PL];
     tm.res_bytes += 8ull * (unsigned long long)((k1 - base + 1) < 64 * PL ? (k1 - base + 1) : 64 * PL);
 #pragma unroll
@@ -1580,9 +1546,6 @@ __device__ inline int32_t binned_resolve(const GraphView &g, const Row &rc, cons
       valid[u] = k <= k1;
       e[u] = e_nx[u]; mwc[u] = mw_nx[u];
     }
-#ifdef SRW_PREFETCH_ROUNDS      // measured and not kept (profiles/r04_table_kernel.md): a round requested ahead is wasted when the answer is in the current one, -9 %
-    if (base + 64 * PL <= k1) fetch_round(base + 64 * PL);
-#endif
 #pragma unroll
     for (int u = 0; u < PL; ++u) {
       xs[u] = (uint32_t)((int64_t)e[u].id - b.vmin); in[u] = false;
@@ -1729,14 +1692,14 @@ __device__ inline int32_t wave_pick_first(const GraphView &g, const Row &rc, flo
 // same certified evaluation as the table path (exact parallel S and prefix sums under the certificate, divide-free
 // certain-miss / certain-hit compares, the sequential chain otherwise) without a single membership lookup.
 constexpr int MASK_MAX_DEG = 256;       // rows up to 255 candidates: 4 per lane stay in registers
-// NS: slots of 64 candidates the instantiation handles (rows up to 64 * NS candidates); NS = 1 is the straight-line form for the short rows
-template <bool CHAIN = true, int NS = 4>
+template <bool CHAIN = true>
 __device__ inline int32_t wave_pick_masked(const GraphView &g, const Row &rc, const Bias &b, uint32_t inline_mask,
                                            const uint32_t *words, float r, unsigned &fallback, int32_t &id_out) {
+  constexpr int NS = MASK_MAX_DEG / 64;             // slots of 64 candidates
   const int lane = lane_id();
   const Ent *row = g.ent + rc.off;
   const int32_t deg = rc.deg;
-  const int ni = NS == 1 ? 1 : (deg + 63) >> 6;     // <= NS
+  const int ni = (deg + 63) >> 6;                   // <= NS
   float wv[NS]; int32_t idv[NS]; uint32_t mw[NS];
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
@@ -1839,12 +1802,9 @@ __device__ inline int32_t wave_pick_edge_table(const GraphView &g, const Row &rc
   const int32_t dv = uni(rc.deg);
   const uint32_t rflags = uni(rc.flags);
   table = uni(table);
-#ifndef SRW_GEOM_ON_SALU          // (the pair's geometry on the vector unit: 604-607 against 610-614 ms at config 3, profiles/r04_table_kernel_ab_runs.txt; -DSRW_GEOM_ON_SALU: as before)
+  // (the pair's geometry on the vector unit: 604-607 against 610-614 ms at config 3, profiles/r04_table_kernel_ab_runs.txt)
   const PairGeom pgv = eb_pair_geometry(on_vector(dv), on_vector(uni(b.prev_deg)), g.ebp);
   PairGeom pg; pg.csh = uni(pgv.csh); pg.n_bins = uni(pgv.n_bins); pg.cmask = uni((int32_t)pgv.cmask) != 0;
-#else
-  const PairGeom pg = eb_pair_geometry(dv, uni(b.prev_deg), g.ebp);
-#endif
   BinGeom geo; geo.csh = pg.csh; geo.n_bins = pg.n_bins;
   const unsigned long long *cmask = nullptr;
   if (pg.cmask) cmask = reinterpret_cast<const unsigned long long *>(table + (size_t)eb_layout(g.ebp.f32 && (rflags & ROW_PQ_F32), pg.n_bins, true, dv,

@@ -69,8 +69,7 @@ def run(budget=60.0, seed=1, eng=None, giant=False, kernels=False):
             # the table walk's kernels (round 6): the default picks by the tables' geometry; the others are forced through their switches,
             # with the default tables and with a table for every certified pair (chunks of 4 candidates)
             if kernels:
-                for env in ({"SRW_TABLE_LANES": "-1"}, {"SRW_TABLE_LANES": "3"}, {"SRW_TABLE_LANES": "2", "SRW_LANE_CSH": "8"}, {"SRW_TABLE_LANES": "0"},
-                            {"SRW_TABLE_GROUPS": "1", "SRW_TABLE_LANES": "-1"}, {"SRW_TABLE_ROUNDS": "1"}):
+                for env in ({"SRW_TABLE_LANES": "-1"}, {"SRW_TABLE_LANES": "3"}, {"SRW_TABLE_LANES": "2", "SRW_LANE_CSH": "8"}, {"SRW_TABLE_LANES": "0"}):
                     variants.append(dict(_env=env))
                     variants.append(dict(_env=env, edge_tables_all=True))
             for v in variants:

@@ -374,13 +374,11 @@ def test_mapped_table_buffer_gives_its_memory_back():
     assert f5 >= f0 - (1 << 30), (f0, f5)               # everything is back once the engine is closed (what stays: the runtime's own pools — kernel scratch, code objects)
 
 
-@pytest.mark.parametrize("kernel", [{}, {"SRW_TABLE_LANES": "3"}, {"SRW_TABLE_LANES": "0"}, {"SRW_TABLE_LANES": "2", "SRW_LANE_CSH": "8"}, {"SRW_TABLE_GROUPS": "1", "SRW_TABLE_LANES": "-1"},
-                                    {"SRW_TABLE_ROUNDS": "1"}, {"SRW_TABLE_ROUNDS": "1", "SRW_LANE_CSH": "8"}])
+@pytest.mark.parametrize("kernel", [{}, {"SRW_TABLE_LANES": "3"}, {"SRW_TABLE_LANES": "0"}, {"SRW_TABLE_LANES": "2", "SRW_LANE_CSH": "8"}])
 def test_table_kernels_walk_every_walker_alike(oracle, monkeypatch, kernel):
-    """The table walk has three kernels: one walker per wave (k_walk_tables, SRW_TABLE_LANES=-1: the reference here), one per lane
+    """The table walk has two kernels: one walker per wave (k_walk_tables, SRW_TABLE_LANES=-1: the reference here) and one per lane
     (walk_lanes.hip: the default — {} — where the tables' chunks are 64 candidates; modes: rows + tables per lane, every step served by the
-    wave, located chunks up to 256 candidates per lane) and one per 16 lanes (walk_groups.hip, opt-in) — profiles/r06_lane_kernel.md,
-    r06_group_kernel.md.  EVERY walker as the wave kernel walks it — weighted and unit-weight, undirected and directed, three-level tables, chunk masks off, and with every
+    wave, located chunks up to 256 candidates per lane) — profiles/r06_lane_kernel.md.  EVERY walker as the wave kernel walks it — weighted and unit-weight, undirected and directed, three-level tables, chunk masks off, and with every
     table step on a long row treated as a boundary draw (the tie list + the chain kernels) — and a sample against the oracle."""
     rng = np.random.default_rng(77)
     cases = [("w", False, 14, (0.25, 4.0), {}), ("", False, 14, (4.0, 0.5), {}), ("w", True, 13, (0.5, 2.0), {}),

@@ -167,13 +167,13 @@ def test_list_rows_equal_the_full_walk_rows(oracle, graph):
                     assert_rows((paths, lens), rows_of_full(full_p, full_l, verts, S, 3), (graph, fam, d, lname))
 
 
-TABLE_KERNELS = [{}, {"SRW_TABLE_LANES": "-1"}, {"SRW_TABLE_GROUPS": "1", "SRW_TABLE_LANES": "-1"}, {"SRW_TABLE_ROUNDS": "1"}]
+TABLE_KERNELS = [{}, {"SRW_TABLE_LANES": "-1"}]
 
 
 @pytest.mark.parametrize("kernel", TABLE_KERNELS)
 @pytest.mark.parametrize("graph", ["multigraph_all", "rmat14_generated"])
 def test_list_rows_equal_the_full_walk_rows_per_edge_tables(monkeypatch, graph, kernel):
-    """Per-edge tables, under every form of the table walk (one walker per lane — the default here —, per wave, per 16 lanes, in rounds):
+    """Per-edge tables, under both forms of the table walk (one walker per lane — the default here — and per wave):
     the small graph with a table for every certified pair (edge_tables_all), weighted RMAT-14 with the default selection."""
     rng = np.random.default_rng(31)
     with pkg().Engine(device=0) as e:
