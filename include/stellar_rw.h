@@ -474,6 +474,51 @@ typedef struct { int32_t context; int32_t num_negatives; uint32_t seed; uint32_t
 int32_t srw_skipgram_batch(srw_handle *h, const void *d_paths, const void *d_lens, int64_t n, int64_t stride,
                            const srw_skipgram_batch_params *bp, void *d_pos, void *d_neg, int64_t cap_windows,
                            int64_t *n_windows);
+/* ---- the negative-sampling training step over those batches (single-GPU handles) ------------------------------------------
+ * What consumes pos [W][context] / neg [W][num_negatives]: one step of skip-gram with negative sampling on the CALLER's two embedding
+ * tables, float32 [nV][dim], row-major, in device memory on the handle's GPU.  Rows are indexed by position in V (the ascending list
+ * srw_graph_vertices returns), as the weights and counts above are; pos and neg hold vertex ids exactly as srw_skipgram_windows /
+ * srw_skipgram_batch write them (the input ids, also on a graph with compacted ids); slot(id) is the id's position in V.
+ * For window w:
+ *   c      = slot(pos[w][center]), 0 <= center < context (0: the first vertex of the window is the centre, as PyG's Node2Vec samples;
+ *            context / 2: the symmetric window)
+ *   t_i    = the other context - 1 entries of pos[w], in order, with label 1, then the num_negatives entries of neg[w], with label 0
+ *   f_i    = sum_d in[c][d] * out[t_i][d]
+ *   g_i    = label_i - sigma(f_i)
+ *   out_new[t_i][:] += lr * g_i * in[c][:]              for every i
+ *   in_new[c][:]    += lr * sum_i g_i * out[t_i][:]
+ *   loss[w] = sum_i softplus(-f_i) (label 1) or softplus(+f_i) (label 0), softplus(x) = log(1 + e^x), evaluated in a form that stays
+ *            finite for any finite f.
+ * There is NO clamp of f to +-6 and NO sigmoid table: this deliberately differs from word2vec.c (and from srw_w2v_fit above, which
+ * restates it) — sigma and softplus are evaluated for the f that was computed, so that every output element can be held against a
+ * float64 restatement of the lines above (tests/sgns_ref.py).
+ * Every READ is from the old tables d_in / d_out, every ADD goes into the new tables.  Duplicates are simply more terms: a negative
+ * equal to a context vertex, the same target twice, a target equal to the centre when one table serves both roles.
+ *   exact step     d_in_new / d_out_new are separate buffers the caller initialised — clones of the old tables (the synchronous
+ *                  mini-batch step) or zeros (with lr = -1 they then receive dLoss/d in and dLoss/d out, Loss = sum_w loss[w]).  The
+ *                  result is a sum of well-defined terms and depends on the order of the additions only (float atomics: the last
+ *                  bits may differ from run to run).
+ *   in place       d_in_new == d_out_new == NULL: the adds go into d_in / d_out themselves (Hogwild).  Where no table row is named
+ *                  twice in the whole call the result is the exact step's; where rows repeat, which value a read sees is unspecified,
+ *                  as in word2vec.c across threads.  No add is lost: the adds are float atomics.
+ * d_in == d_out is allowed (one table for both roles, as PyG's Node2Vec); then d_in_new == d_out_new is required.  Passing the old
+ * table's own address as its new table is the in-place form of that table.  Any other overlap between the byte ranges of two of the
+ * four tables, and any overlap of d_loss with one of them, is SRW_ERR_INVALID.
+ * A window that holds an id which is no present vertex of the graph (below the smallest or above the largest id, in a gap, -1) is
+ * skipped whole: it makes no add, its loss[w] is 0 and it is counted in *n_skipped.  No id reaches an address before its position has
+ * been checked against nV, so no tensor content can send a store outside a table.
+ * d_loss: float32 [n_windows] in device memory, overwritten, or NULL.  n_skipped may be NULL.  The call runs on the handle's stream and
+ * is complete on return; the skip count (8 bytes) is the only read-back.  Every offset is 64-bit.
+ * SRW_ERR_INVALID before anything is launched, the tables untouched: a NULL h / sp; no graph loaded, a sharded handle (world > 1),
+ * population 1 selected; n_rows != nV; dim not a multiple of 64 in 64 .. 512; context < 1, num_negatives < 0, context + num_negatives
+ * < 2 or > 64; center outside [0, context); a non-finite lr; reserved != 0; n_windows < 0; then, for n_windows > 0: a NULL d_pos /
+ * d_in / d_out; num_negatives > 0 with d_neg == NULL; exactly one of d_in_new / d_out_new NULL; a pointer that is not aligned to 4
+ * bytes; the overlap rules above.  n_windows == 0 is SRW_OK whatever the pointers are (an empty tensor's are arbitrary): nothing is
+ * launched, *n_skipped = 0. */
+typedef struct { int32_t context; int32_t num_negatives; int32_t dim; int32_t center; float lr; int32_t reserved; } srw_sgns_params;   /* 24 bytes */
+int32_t srw_sgns_step(srw_handle *h, const void *d_pos, const void *d_neg, int64_t n_windows, const srw_sgns_params *sp,
+                      const void *d_in, const void *d_out, void *d_in_new, void *d_out_new, int64_t n_rows,
+                      void *d_loss /* float32 [n_windows] or NULL */, int64_t *n_skipped /* or NULL */);
 /* Unit-test hook (host only, no GPU): word2vec.c's CreateBinaryTree as the trainer uses it.  counts[n_vocab] in descending order ->
  * code_len[n_vocab], codes[n_vocab][40] (bits, root first), points[n_vocab][40] (rows of syn1 on the path, root = n_vocab - 2 first;
  * -1 beyond the code).  Known answers: tests/test_w2v_known_answers.py. */

@@ -57,6 +57,11 @@ class SkipgramBatchParams(C.Structure):
                 ("exclude_window", C.c_int32), ("max_draws", C.c_int32)]
 
 
+class SgnsParams(C.Structure):
+    _fields_ = [("context", C.c_int32), ("num_negatives", C.c_int32), ("dim", C.c_int32), ("center", C.c_int32),
+                ("lr", C.c_float), ("reserved", C.c_int32)]
+
+
 class SrwError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("srw error %d: %s" % (code, msg))
@@ -104,7 +109,7 @@ EXPORTS = [
     "srw_cluster_shard", "srw_cluster_load_edgelist", "srw_cluster_load_coo", "srw_cluster_generate_rmat",
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
     "srw_cluster_set_sources", "srw_cluster_clear_sources", "srw_cluster_sources",
-    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_negative_weights_set", "srw_graph_degrees_device", "srw_path_vertex_counts", "srw_skipgram_batch", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
+    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_negative_weights_set", "srw_graph_degrees_device", "srw_path_vertex_counts", "srw_skipgram_batch", "srw_sgns_step", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
     "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
 
@@ -192,6 +197,7 @@ def lib():
     L.srw_graph_degrees_device.argtypes = [vp, vp]
     L.srw_path_vertex_counts.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, i64p]
     L.srw_skipgram_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(SkipgramBatchParams), vp, vp, C.c_int64, i64p]
+    L.srw_sgns_step.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(SgnsParams), vp, vp, vp, vp, C.c_int64, vp, i64p]
     L.srw_w2v_save_words.argtypes = [C.POINTER(C.c_char_p), f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
     L.srw_w2v_huffman.argtypes = [C.POINTER(C.c_int64), C.c_int64, i32p, C.POINTER(C.c_uint8), i32p]
     L.srw_w2v_save.argtypes = [i32p, f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
@@ -791,6 +797,112 @@ class Engine:
         exclude_window=exclude_window, max_draws=max_draws) over the result where it lies — walk_skipgram with the weighted draw."""
         self.walk(fetch=False, sources=sources, **walk_kw)
         return self.skipgram_batch(context, num_negatives, seed=sg_seed, epoch=epoch, exclude_window=exclude_window, max_draws=max_draws)
+
+    # ---- the negative-sampling training step over those batches (srw_sgns_step; DESIGN 7e) ----
+    def _sgns_args(self, what, pos, neg, emb_in, emb_out, into):
+        """The tensor checks of sgns_step: TypeError before the library is called -> (W, C, K, nV, D, device)."""
+        is_t = lambda x: hasattr(x, "data_ptr") and hasattr(x, "is_cuda")      # noqa: E731
+        ids = [("pos", pos)] + ([("neg", neg)] if neg is not None else [])
+        tabs = [("emb_in", emb_in), ("emb_out", emb_out)]
+        if into is not None:
+            if not (isinstance(into, (tuple, list)) and len(into) == 2):
+                raise TypeError("%s: into must be a pair (new_in, new_out)" % what)
+            tabs += [("into[0]", into[0]), ("into[1]", into[1])]
+        for name, t in ids + tabs:
+            if not is_t(t):
+                raise TypeError("%s: %s must be a torch tensor" % (what, name))
+        # (shape, contiguity and dtype first, the device last — skipgram's order: each refusal can be met without a GPU)
+        if pos.dim() != 2 or (neg is not None and (neg.dim() != 2 or neg.shape[0] != pos.shape[0])):
+            raise TypeError("%s: pos must be [W, C] and neg [W, K] (got %s, %s)"
+                            % (what, tuple(pos.shape), None if neg is None else tuple(neg.shape)))
+        if emb_in.dim() != 2 or any(tuple(t.shape) != tuple(emb_in.shape) for _, t in tabs):
+            raise TypeError("%s: the tables must all be [nV, D] (got %s)" % (what, ", ".join(str(tuple(t.shape)) for _, t in tabs)))
+        for name, t in ids + tabs:
+            if not t.is_contiguous():
+                raise TypeError("%s: %s must be contiguous" % (what, name))
+        for name, t in ids:
+            if str(t.dtype) != "torch.int32":
+                raise TypeError("%s: %s must be torch.int32 (got %s)" % (what, name, t.dtype))
+        for name, t in tabs:
+            if str(t.dtype) != "torch.float32":
+                raise TypeError("%s: %s must be torch.float32 (got %s)" % (what, name, t.dtype))
+        mine = getattr(self, "device", None)
+        for name, t in ids + tabs:
+            if not t.is_cuda:
+                raise TypeError("%s: %s must be in device memory (got %s)" % (what, name, t.device))
+            if t.device != pos.device or (mine is not None and t.device.index != mine):
+                raise TypeError("%s: the tensors must be on the handle's device (cuda:%s), got %s for %s" % (what, mine, t.device, name))
+        return (int(pos.shape[0]), int(pos.shape[1]), 0 if neg is None else int(neg.shape[1]), int(emb_in.shape[0]),
+                int(emb_in.shape[1]), pos.device)
+
+    def sgns_step(self, pos, neg, emb_in, emb_out, lr, center=0, into=None, loss=False):
+        """One skip-gram negative-sampling step over (pos, neg) as skipgram / skipgram_batch return them, on the caller's tables
+        emb_in / emb_out: float32 [nV, D] on the handle's device, rows in the order of vertices(), D a multiple of 64 up to 512.  For
+        every window: centre = pos[w, center], the other entries of pos[w] are targets with label 1, neg[w] (None: K = 0) targets with
+        label 0; f = <emb_in[centre], emb_out[target]>, g = label - sigmoid(f); emb_out[target] += lr g emb_in[centre] and
+        emb_in[centre] += lr sum g emb_out[target], every read from the values before the call (include/stellar_rw.h; no clamp at
+        +-6, no sigmoid table).  into=None: in place (Hogwild: where rows repeat in the call a read may see another window's add;
+        no add is lost).  into=(new_in, new_out): the exact step — every add goes into these tensors (clones of the tables, or
+        zeros), the tables themselves are only read.  emb_in may be emb_out (one table for both roles); then new_in must be new_out.
+        A window that holds an id which is no vertex of the graph is skipped whole.  Returns (loss, n_skipped): loss is a float32
+        tensor [W] of the windows' losses at the old values when loss=True, else None.  Tensor checks raise TypeError before the
+        library is called; the synchronisation rule is skipgram_batch's (torch's stream is waited for, the call is complete on
+        return)."""
+        import torch
+        W, C_, K, nV, D, dev = self._sgns_args("sgns_step", pos, neg, emb_in, emb_out, into)
+        out_loss = torch.empty((W,), dtype=torch.float32, device=dev) if loss else None
+        sp = SgnsParams(C_, K, D, int(center), float(lr), 0)
+        skipped = C.c_int64(0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())          # noqa: E731
+        torch.cuda.current_stream(dev).synchronize()                     # the tensors are written before the handle's stream reads them
+        self._ck(lib().srw_sgns_step(self.h, ptr(pos), ptr(neg), W, C.byref(sp), ptr(emb_in), ptr(emb_out),
+                                     ptr(into[0]) if into is not None else None, ptr(into[1]) if into is not None else None,
+                                     nV, ptr(out_loss), C.byref(skipped)))
+        return out_loss, skipped.value
+
+    def sgns_grad(self, pos, neg, emb_in, emb_out, center=0):
+        """(grad_in, grad_out, loss): dLoss/d emb_in and dLoss/d emb_out, Loss = loss.sum(), loss [W] the windows' negative-sampling
+        losses — sgns_step's exact form into zeroed tables with lr = -1: what the backward of a torch.autograd.Function returns.
+        With emb_in is emb_out (one table for both roles) grad_in is grad_out: the one table's gradient."""
+        import torch
+        self._sgns_args("sgns_grad", pos, neg, emb_in, emb_out, None)
+        grad_in = torch.zeros_like(emb_in)
+        grad_out = grad_in if emb_out.data_ptr() == emb_in.data_ptr() else torch.zeros_like(emb_out)
+        loss, _ = self.sgns_step(pos, neg, emb_in, emb_out, -1.0, center=center, into=(grad_in, grad_out), loss=True)
+        return grad_in, grad_out, loss
+
+    def train_sgns(self, dim, context, num_negatives, epochs, batch_sources, lr=0.025, seed=1, **walk_kw):
+        """node2vec with negative sampling, everything on the device: per epoch the vertices are shuffled (a torch generator seeded
+        with `seed`), per batch of batch_sources start vertices one walk_skipgram_batch (epoch = the step number, sg_seed = seed; the
+        negatives follow the weight table in force) and one sgns_step in place (center 0), the learning rate decaying linearly from lr
+        to 1e-4 lr over all steps.  emb_in starts uniform in (-0.5, 0.5) / dim, emb_out at zero (word2vec's start).  walk_kw goes to
+        walk(); epoch k walks iterations first_walk + k * num_walks onwards, so every epoch sees fresh walks from the same seed.
+        Returns (emb_in, emb_out, mean loss per window of every epoch); rows in the order of vertices()."""
+        import torch
+        dev = torch.device("cuda", getattr(self, "device", None) or 0)
+        V = torch.as_tensor(self.vertices(), dtype=torch.int32)
+        nV = int(V.numel())
+        gen = torch.Generator().manual_seed(int(seed))
+        emb_in = ((torch.rand((nV, dim), generator=gen, dtype=torch.float32) - 0.5) / dim).to(dev)
+        emb_out = torch.zeros((nV, dim), dtype=torch.float32, device=dev)
+        per_epoch = (nV + batch_sources - 1) // batch_sources if nV else 0
+        total, step, means = max(per_epoch * epochs, 1), 0, []
+        first, per_call = int(walk_kw.pop("first_walk", 0)), int(walk_kw.get("num_walks", 1))
+        for k in range(epochs):
+            order = V[torch.randperm(nV, generator=gen)].to(dev)
+            loss_sum, n_win = 0.0, 0
+            for b in range(per_epoch):
+                pos, neg = self.walk_skipgram_batch(order[b * batch_sources:(b + 1) * batch_sources].contiguous(), context, num_negatives,
+                                                    sg_seed=seed, epoch=step, first_walk=first + k * per_call, **walk_kw)
+                rate = max(lr * (1.0 - step / total), lr * 1e-4)
+                step += 1
+                if pos.shape[0] == 0:
+                    continue
+                loss, _ = self.sgns_step(pos, neg, emb_in, emb_out, rate, loss=True)
+                loss_sum += float(loss.double().sum())
+                n_win += int(pos.shape[0])
+            means.append(loss_sum / max(n_win, 1))
+        return emb_in, emb_out, means
 
     def write_paths(self, output_dir, n_parts=1, write_crc=False):
         self._ck(lib().srw_write_paths(self.h, os.fsencode(output_dir), n_parts, int(write_crc)))

@@ -746,6 +746,51 @@ int32_t srw_skipgram_batch(srw_handle *h, const void *d_paths, const void *d_len
   });
 }
 
+int32_t srw_sgns_step(srw_handle *h, const void *d_pos, const void *d_neg, int64_t n_windows, const srw_sgns_params *sp,
+                      const void *d_in, const void *d_out, void *d_in_new, void *d_out_new, int64_t n_rows, void *d_loss,
+                      int64_t *n_skipped) {
+  if (!h || !sp) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_single_gpu(h, "srw_sgns_step");
+    need(h->g.loaded, "srw_sgns_step: no graph loaded");
+    if (n_rows != h->g.n_vertices)
+      throw Error(SRW_ERR_INVALID, "srw_sgns_step: tables of n_rows = " + std::to_string(n_rows) + " for " + std::to_string(h->g.n_vertices) + " vertices");
+    need(sp->dim >= 64 && sp->dim <= 512 && sp->dim % 64 == 0, "srw_sgns_step: dim must be a multiple of 64 in 64 .. 512");
+    need(sp->context >= 1, "srw_sgns_step: context < 1");
+    need(sp->num_negatives >= 0, "srw_sgns_step: num_negatives < 0");
+    need(sp->context <= 64 && sp->num_negatives <= 64 && sp->context + sp->num_negatives >= 2 && sp->context + sp->num_negatives <= 64,
+         "srw_sgns_step: context + num_negatives must be in 2 .. 64 (one id per lane of a wave)");
+    need(sp->center >= 0 && sp->center < sp->context, "srw_sgns_step: center outside [0, context)");
+    need(std::isfinite(sp->lr), "srw_sgns_step: lr is not finite");
+    need(sp->reserved == 0, "srw_sgns_step: reserved != 0");
+    need(n_windows >= 0, "srw_sgns_step: n_windows < 0");
+    if (n_windows == 0) { if (n_skipped) *n_skipped = 0; return; }     // an empty tensor's pointers are arbitrary; nothing to launch
+    need(d_pos && d_in && d_out, "srw_sgns_step: one of d_pos / d_in / d_out is null");
+    need(sp->num_negatives == 0 || d_neg, "srw_sgns_step: num_negatives > 0 and d_neg is null");
+    need((d_in_new == nullptr) == (d_out_new == nullptr), "srw_sgns_step: exactly one of d_in_new / d_out_new is null (both: in place)");
+    void *in_new = d_in_new ? d_in_new : const_cast<void *>(d_in), *out_new = d_out_new ? d_out_new : const_cast<void *>(d_out);
+    need((((uintptr_t)d_pos | (uintptr_t)d_neg | (uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)in_new | (uintptr_t)out_new |
+           (uintptr_t)d_loss) & 3u) == 0, "srw_sgns_step: a pointer is not aligned to 4 bytes");
+    // two tables are the same table or apart; the same only as the in-place form of a role or as one table for both roles
+    const uintptr_t bytes = (uintptr_t)n_rows * (uintptr_t)sp->dim * 4u;
+    const uintptr_t t[4] = {(uintptr_t)d_in, (uintptr_t)d_out, (uintptr_t)in_new, (uintptr_t)out_new};
+    for (int i = 0; i < 4; ++i)
+      for (int j = i + 1; j < 4; ++j)
+        need(t[i] == t[j] || t[i] + bytes <= t[j] || t[j] + bytes <= t[i], "srw_sgns_step: two tables overlap without being the same table");
+    if (d_loss) {                                      // the losses are written while the tables are read and added to
+      const uintptr_t l = (uintptr_t)d_loss, lbytes = (uintptr_t)n_windows * 4u;
+      for (int i = 0; i < 4; ++i) need(l + lbytes <= t[i] || t[i] + bytes <= l, "srw_sgns_step: d_loss overlaps a table");
+    }
+    const bool one_table = t[0] == t[1];
+    need(!one_table || t[2] == t[3], "srw_sgns_step: d_in == d_out needs d_in_new == d_out_new");
+    need(one_table || (t[2] != t[3] && t[2] != t[1] && t[3] != t[0]),
+         "srw_sgns_step: a new table is another role's table (only d_in == d_out shares one table between the roles)");
+    const int64_t skipped = sgns_step(h, (const int32_t *)d_pos, (const int32_t *)d_neg, n_windows, *sp, (const float *)d_in,
+                                      (const float *)d_out, (float *)in_new, (float *)out_new, (float *)d_loss);
+    if (n_skipped) *n_skipped = skipped;
+  });
+}
+
 int32_t srw_w2v_huffman(const int64_t *counts, int64_t n_vocab, int32_t *code_len, uint8_t *codes, int32_t *points) {
   if (!counts || !code_len || !codes || !points || n_vocab < 0) return SRW_ERR_INVALID;
   try { w2v_huffman(counts, n_vocab, code_len, codes, points); return SRW_OK; }

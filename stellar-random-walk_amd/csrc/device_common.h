@@ -347,4 +347,31 @@ __host__ __device__ inline int32_t owner_of_tab(int32_t v, int32_t world, const 
   return owner_of(v, world);
 }
 
+// first index of [a, a + n) whose value is >= key (a ascending)
+__device__ inline int64_t lower_bound_i32(const int32_t *__restrict__ a, int64_t n, int32_t key) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// The slot of a vertex id as a caller's tensor spells it (the input id, also on a graph with compacted ids: orig_id != nullptr is the
+// rank array), or n_slots when the id is no present vertex of the graph: below vmin, above vmax, in a gap of the id space.  What comes
+// back is < n_slots or == n_slots, never anything else: the only value a caller may index rows-sized arrays with is the former.
+__device__ inline int64_t vertex_slot(int32_t id, const Row *__restrict__ rows, const int32_t *__restrict__ orig_id, int64_t n_slots,
+                                      int32_t vmin) {
+  int64_t s;
+  if (orig_id) {
+    const int64_t k = lower_bound_i32(orig_id, n_slots, id);
+    s = (k < n_slots && orig_id[k] == id) ? k : n_slots;
+  } else {
+    s = (int64_t)id - vmin;
+    if (s < 0 || s >= n_slots) s = n_slots;
+  }
+  if (s < n_slots && !(rows[s].flags & ROW_PRESENT)) s = n_slots;
+  return s;
+}
+
 }  // namespace srw

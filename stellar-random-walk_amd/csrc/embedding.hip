@@ -128,21 +128,7 @@ __device__ inline float wave_sum_f32_dpp(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// Four sums over the wave at the price of one and a half: two quad exchanges leave lane l with the quad's partial sum of value (l & 3),
-// two row shifts by multiples of four add the quads of a row (lanes 12..15 hold the row's), two butterflies add the rows.
-template <int CTRL>
-__device__ inline float dpp_mov_f32(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-__device__ inline float wave_sum4_f32(float a, float b, float c, float d, int lane) {
-  const bool odd = (lane & 1) != 0, hi = (lane & 2) != 0;
-  const float ab = (odd ? b : a) + dpp_mov_f32<0xB1>(odd ? a : b);        // quad_perm [1,0,3,2]: even lanes a-pairs, odd lanes b-pairs
-  const float cd = (odd ? d : c) + dpp_mov_f32<0xB1>(odd ? c : d);
-  float x = (hi ? cd : ab) + dpp_mov_f32<0x4E>(hi ? ab : cd);             // quad_perm [2,3,0,1]: lane & 3 -> a, b, c, d over the quad
-  x += dpp_mov_f32<0x114>(x);                                             // row_shr:4, row_shr:8 (lanes without a source add 0)
-  x += dpp_mov_f32<0x118>(x);
-  x += __shfl_xor(x, 16);
-  x += __shfl_xor(x, 32);
-  return x;
-}
+// (the four-sums-in-one reduction of the node groups below, wave_sum4_f32, is in wave_primitives.h: sgns.hip reduces its targets with it)
 
 // The training kernel (round 5).  MLlib's loop (and word2vec.c's) visits, for ONE position, every context word of the window and for
 // each of them every Huffman node of the CENTRE word: the same <= 40 rows of syn1, read and written once per context — ~11 times at

@@ -139,6 +139,9 @@ struct Graph {
   DevBuf<uint64_t> neg_cdf;       // [n_vertices] inclusive prefix sums of the weights
   DevBuf<uint32_t> neg_guide;     // [2^neg_gbits + 1] index selected by the draw b << (64 - neg_gbits); the last entry: by t = T - 1
   uint64_t neg_total = 0; int32_t neg_gbits = 0; bool has_neg = false;
+  // srw_sgns_step (sgns.hip): position in V of every slot's vertex, -1 for a slot that is no present vertex; built at the first step
+  DevBuf<int32_t> vpos;           // [n_slots]
+  bool has_vpos = false;
   std::vector<int32_t> part_of;   // VCut: last pId recorded per dst slot, -1 none (host side; empty if unused)
   GraphView view() const { return GraphView{rows.p, ent.p, sids.p, sperm.p, has_fo ? fo.p : nullptr, (has_cfo || cfo_linked || has_cfo_local) ? cfo.p : nullptr, has_al ? al.p : nullptr, has_al ? rsum.p : nullptr,
                      mrows.p ? mrows.p : rows.p, msids.p ? msids.p : sids.p, (has_pq && pq_unit == 0.0) ? pq.p : nullptr, has_pq ? pq_ok.p : nullptr, (has_ehash && use_ehash) ? ehash.p : nullptr, ehash_mask,
@@ -193,6 +196,7 @@ struct srw_handle {
   srw::DevBuf<int64_t> sg_off;                   // srw_skipgram_windows: first window of every row [n + 1] ...
   srw::DevBuf<char> sg_temp;                     // ... and rocprim's temporary storage (both kept between calls: one call per training step)
   srw::DevBuf<unsigned long long> vc_slots;      // srw_path_vertex_counts: occurrences per slot [n_slots], then the ids that are no vertex [1]
+  srw::DevBuf<unsigned long long> sgns_skipped;  // srw_sgns_step: windows skipped for an id that is no present vertex [1]
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
   // srw_cluster_set_sources: the entries of the cluster's list that THIS shard owns, in list order (shard_set_sources, sources.hip):
@@ -301,6 +305,12 @@ class PathWriter {
 // ---- edgelist_device.hip ----
 // Device-side tokenizer for two-column integer edge lists (+ a short decimal weight column); false = not that shape (or any doubt): use the host tokenizer.
 bool load_edgelist_device(srw_handle *h, const char *path, bool directed, bool weighted);
+
+// ---- sgns.hip ----
+// srw_sgns_step behind its argument checks (api.cpp; the new tables are never null here: in place = the old tables), on the handle's
+// stream, complete on return -> windows skipped for an id that is no present vertex
+int64_t sgns_step(srw_handle *h, const int32_t *d_pos, const int32_t *d_neg, int64_t n_windows, const srw_sgns_params &sp,
+                  const float *d_in, const float *d_out, float *d_in_new, float *d_out_new, float *d_loss);
 
 // ---- sources.hip ----
 // The list of start vertices of the next walks: h_ids (host) or d_ids (on the handle's device), n entries.  Throws SRW_ERR_INVALID and

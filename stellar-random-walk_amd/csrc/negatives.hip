@@ -177,16 +177,6 @@ void launch_draw_g(srw_handle *h, const DrawArgs &a, int G) {
 }
 
 // ---- counts ----
-// first index of [a, a + n) whose value is >= key (a ascending)
-__device__ inline int64_t lower_bound_i32(const int32_t *__restrict__ a, int64_t n, int32_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // slots[n_slots + 1] (zeroed by the caller): occurrences per slot; slots[n_slots]: ids that are no vertex of the graph
 __global__ __launch_bounds__(NG_TPB) void k_vertex_count(const int32_t *__restrict__ paths, const int32_t *__restrict__ lens, int64_t n,
                                                          int64_t stride, const Row *__restrict__ rows, const int32_t *__restrict__ orig_id,
@@ -204,15 +194,7 @@ __global__ __launch_bounds__(NG_TPB) void k_vertex_count(const int32_t *__restri
     if (in) {
       const int32_t l = lens[r] < stride ? lens[r] : (int32_t)stride;
       if (c < l) {
-        const int32_t id = paths[r * stride + c];
-        if (orig_id) {
-          const int64_t k = lower_bound_i32(orig_id, n_slots, id);
-          s = (k < n_slots && orig_id[k] == id) ? k : n_slots;
-        } else {
-          s = (int64_t)id - vmin;
-          if (s < 0 || s >= n_slots) s = n_slots;
-        }
-        if (s < n_slots && !(rows[s].flags & ROW_PRESENT)) s = n_slots;
+        s = vertex_slot(paths[r * stride + c], rows, orig_id, n_slots, vmin);   // (device_common.h: k_sgns_step resolves the same way)
       }
     }
     // equal slots of the wave are added once: up to VC_ROUNDS leaders, then every lane that is left for itself

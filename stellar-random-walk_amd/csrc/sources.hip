@@ -20,16 +20,6 @@ namespace {
 constexpr int TPB = 256;
 constexpr unsigned long long NO_BAD = ~0ull;
 
-// first index of [a, a + n) whose value is >= key (a ascending)
-__device__ inline int64_t lower_bound_i32(const int32_t *__restrict__ a, int64_t n, int32_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // One lane per list entry.  ids[i] is a vertex id as the input spelled it; out[i] receives the entry of the handle's vertex list
 // (verts[n_verts], ascending: ids, or slots when orig_id != nullptr) that stands for it.  An id that is no vertex of the graph
 // leaves out[i] = vmin (never read: the call fails) and lowers *bad to (position << 32 | id): the smallest word names the first one.

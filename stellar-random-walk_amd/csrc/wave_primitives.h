@@ -74,6 +74,23 @@ __device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
   return (unsigned long long)uni((int64_t)v);
 }
 
+// Four sums over the wave at the price of one and a half: two quad exchanges leave lane l with the quad's partial sum of value (l & 3),
+// two row shifts by multiples of four add the quads of a row (lanes 12..15 hold the row's), two butterflies add the rows: lanes 12..15
+// of every row end up with the wave's sums of a, b, c, d.  (embedding.hip: the nodes of a context; sgns.hip: the targets of a window)
+template <int CTRL>
+__device__ inline float dpp_mov_f32(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
+__device__ inline float wave_sum4_f32(float a, float b, float c, float d, int lane) {
+  const bool odd = (lane & 1) != 0, hi = (lane & 2) != 0;
+  const float ab = (odd ? b : a) + dpp_mov_f32<0xB1>(odd ? a : b);        // quad_perm [1,0,3,2]: even lanes a-pairs, odd lanes b-pairs
+  const float cd = (odd ? d : c) + dpp_mov_f32<0xB1>(odd ? c : d);
+  float x = (hi ? cd : ab) + dpp_mov_f32<0x4E>(hi ? ab : cd);             // quad_perm [2,3,0,1]: lane & 3 -> a, b, c, d over the quad
+  x += dpp_mov_f32<0x114>(x);                                             // row_shr:4, row_shr:8 (lanes without a source add 0)
+  x += dpp_mov_f32<0x118>(x);
+  x += __shfl_xor(x, 16);
+  x += __shfl_xor(x, 32);
+  return x;
+}
+
 // Exactness certificate for a sum of f32 values widened to f64.
 // Every nonzero finite f32 x with unbiased exponent e is an integer multiple of 2^(max(e,-126)-23).  If all
 // addends are multiples of u = 2^ue_min and n * 2^(e_max+1) <= 2^53 * u, then every partial sum, in any
