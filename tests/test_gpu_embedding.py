@@ -71,9 +71,14 @@ def test_vocabulary_built_in_chunks_is_the_same_vocabulary(eng, oracle, monkeypa
 
 @pytest.mark.parametrize("dim,n_words", [(96, 27), (160, 26), (40, 20)])
 def test_deep_huffman_codes(eng, oracle, dim, n_words):
-    """Fibonacci counts give the deepest tree a vocabulary can have (code length n_words - 1): the rare words' codes are longer than the
-    rows the training kernel keeps in registers (24 at dim <= 128 and <= 256, 32 at dim <= 64), so their last nodes take the memory
-    path; the frequent words' codes are one or two nodes (groups with empty slots)."""
+    """Fibonacci counts give the deepest tree a vocabulary can have (code length n_words - 1): the frequent words' codes are one or two
+    nodes (groups with empty slots), and the run must come out finite and within the tolerance at that depth — that much this test
+    sees.  The rare words' codes are longer than the rows the training kernel keeps in registers (24 at dim 65 .. 256, 32 at dim
+    <= 64), so their last nodes take the memory path (at (96, 27) and (160, 26); at (40, 20) no code passes 32 rows) — but a wrong
+    update THERE this test cannot see: the words that deep occur once or twice in 3e5 tokens, syn1 starts at zero, so the first visit
+    of a node adds nothing to syn0; with the last node of every code longer than 24 dropped, no element of the (160, 26) result moves
+    by more than 1.8e-6 (float64 restatement, tests/w2v_ref.py: mutate="tail_last", reg_rows=24), against an atol of 5e-4.  The same lines of the kernel are held
+    where deep nodes are visited often, at 8 and 4 register rows: tests/test_gpu_embedding_exact.py (fib13x8, fib9x16, residues)."""
     fib = [1, 1]
     while len(fib) < n_words:
         fib.append(fib[-1] + fib[-2])
