@@ -519,6 +519,49 @@ typedef struct { int32_t context; int32_t num_negatives; int32_t dim; int32_t ce
 int32_t srw_sgns_step(srw_handle *h, const void *d_pos, const void *d_neg, int64_t n_windows, const srw_sgns_params *sp,
                       const void *d_in, const void *d_out, void *d_in_new, void *d_out_new, int64_t n_rows,
                       void *d_loss /* float32 [n_windows] or NULL */, int64_t *n_skipped /* or NULL */);
+/* ---- asking a table of vectors: the k nearest rows ---------------------------------------------------------------------------
+ * srw_topk_rows: for each of n_queries queries the k best rows of d_table (float32 [n_rows][dim], row-major, device memory on the handle's
+ * GPU), by cosine or by dot product, in ROW space: a table srw_sgns_step trained is in the order of V, srw_w2v_fit's vectors are in
+ * vocabulary order; the search knows neither.  It needs no graph and works on any handle.  The n_queries x n_rows scores are never
+ * formed: the table is read once per pass of up to 32 queries (16 for dim > 256, 8 for dim > 512).
+ * Query forms.
+ *   d_qrow only    query i is table row qrow[i], and that row is excluded from its own result (MLlib's findSynonyms(word)).  A qrow[i]
+ *                  outside [0, n_rows) skips the query: its output row is padding and it is counted in *n_skipped.
+ *   d_qvec only    query i is the vector qvec[i][0 .. dim) and nothing is excluded.
+ *   both           the vector is the query and row qrow[i] is excluded; -1 means none; any other value outside [0, n_rows) skips the
+ *                  query as above.
+ *   neither        SRW_ERR_INVALID when n_queries > 0.
+ * metric 1, dot:    score = sum_d q[d] r[d].
+ * metric 0, cosine: score = dot / (sqrtf(sum q^2) * sqrtf(sum r^2)) with correctly rounded sqrt and divide; the score is exactly 0 when
+ *                  either sum of squares is 0 (as MLlib; a table that starts at zero has such rows).  The row's sum of squares is taken
+ *                  in the same pass, from the row the dot product reads: there is no array of norms to keep in step with the table.
+ * Arithmetic: float32, every sum an fmaf chain over d = 0, 1, ..., dim - 1 starting from 0.  The score of (query, row) depends on those
+ * two vectors alone — not on the row's position in the table, on n_queries, on k, or on which other queries share a pass — so identical
+ * rows get identical score bits and a call repeats bit for bit.  A NaN score ranks, and is returned, as -inf; a score of -0 ranks, and is
+ * returned, as +0.  Inputs whose sums of squares overflow float32 (or whose product of norms underflows to 0) are the caller's problem:
+ * the scores are then whatever inf and NaN make of the formula above.
+ * Order: the k best eligible rows by (score descending, row ascending) — a total order — in that order.  If fewer than k rows are
+ * eligible the tail is padding: row -1, score -inf.  d_rows int32 [n_queries][k], d_scores float32 [n_queries][k], both overwritten.
+ * No tensor content reaches an address unchecked: qrow[i] is compared with n_rows before it is multiplied into one.
+ * The call runs on the handle's stream and is complete on return; the skip count (8 bytes) is the only read-back; n_skipped may be NULL.
+ * Only 4-byte alignment is assumed of any pointer, and dim need not be a multiple of 4.  Every offset is 64-bit.
+ * SRW_ERR_INVALID before anything is launched, the outputs untouched: a NULL h / tp; dim outside 1 .. 1024, k outside 1 .. 64, metric
+ * not 0 or 1, reserved != 0; n_rows < 0 or >= 2^31, n_queries < 0; then, for n_queries > 0: a NULL d_table with n_rows > 0, a NULL
+ * d_rows / d_scores, no query form, a pointer that is not aligned to 4 bytes, an output's byte range overlapping an input's or the other
+ * output's.  n_queries == 0 is SRW_OK whatever the pointers are: nothing is launched, *n_skipped = 0.  n_rows == 0 with n_queries > 0
+ * returns padding only (and, by row, skips every query). */
+typedef struct { int32_t dim; int32_t k; int32_t metric; int32_t reserved; } srw_topk_params;   /* 16 bytes */
+int32_t srw_topk_rows(srw_handle *h, const void *d_table /* float32 [n_rows][dim] */, int64_t n_rows,
+                      const void *d_qvec /* float32 [n_queries][dim] or NULL */, const void *d_qrow /* int32 [n_queries] or NULL */,
+                      int64_t n_queries, const srw_topk_params *tp,
+                      void *d_rows /* int32 [n_queries][k] */, void *d_scores /* float32 [n_queries][k] */,
+                      int64_t *n_skipped /* or NULL */);
+/* Vertex ids to rows of such a table on the device: rows[i] = the position of ids[i] in V (the ascending list srw_graph_vertices
+ * returns), -1 when the id is no vertex of the graph (below the smallest or above the largest id, in a gap); *n_unknown counts those.
+ * ids are the input ids, also on a graph with compacted ids.  d_ids, d_rows: int32 [n] in device memory on the handle's GPU.
+ * SRW_ERR_INVALID as srw_sgns_step: a NULL h, no graph loaded, a sharded handle (world > 1), population 1 selected, n < 0, and for n > 0
+ * a NULL d_ids / d_rows or one that is not aligned to 4 bytes.  n == 0 is SRW_OK (*n_unknown = 0).  Complete on return. */
+int32_t srw_vertex_rows(srw_handle *h, const void *d_ids /* int32 [n] */, int64_t n, void *d_rows /* int32 [n] */, int64_t *n_unknown /* or NULL */);
 /* Unit-test hook (host only, no GPU): word2vec.c's CreateBinaryTree as the trainer uses it.  counts[n_vocab] in descending order ->
  * code_len[n_vocab], codes[n_vocab][40] (bits, root first), points[n_vocab][40] (rows of syn1 on the path, root = n_vocab - 2 first;
  * -1 beyond the code).  Known answers: tests/test_w2v_known_answers.py. */

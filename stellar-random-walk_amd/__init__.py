@@ -62,6 +62,13 @@ class SgnsParams(C.Structure):
                 ("lr", C.c_float), ("reserved", C.c_int32)]
 
 
+class TopkParams(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("k", C.c_int32), ("metric", C.c_int32), ("reserved", C.c_int32)]
+
+
+TOPK_METRICS = {"cosine": 0, "dot": 1}     # srw_topk_params.metric
+
+
 class SrwError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("srw error %d: %s" % (code, msg))
@@ -109,7 +116,7 @@ EXPORTS = [
     "srw_cluster_shard", "srw_cluster_load_edgelist", "srw_cluster_load_coo", "srw_cluster_generate_rmat",
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
     "srw_cluster_set_sources", "srw_cluster_clear_sources", "srw_cluster_sources",
-    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_negative_weights_set", "srw_graph_degrees_device", "srw_path_vertex_counts", "srw_skipgram_batch", "srw_sgns_step", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
+    "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_negative_weights_set", "srw_graph_degrees_device", "srw_path_vertex_counts", "srw_skipgram_batch", "srw_sgns_step", "srw_topk_rows", "srw_vertex_rows", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
     "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
 
@@ -198,6 +205,8 @@ def lib():
     L.srw_path_vertex_counts.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, i64p]
     L.srw_skipgram_batch.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, C.POINTER(SkipgramBatchParams), vp, vp, C.c_int64, i64p]
     L.srw_sgns_step.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(SgnsParams), vp, vp, vp, vp, C.c_int64, vp, i64p]
+    L.srw_topk_rows.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.POINTER(TopkParams), vp, vp, i64p]
+    L.srw_vertex_rows.argtypes = [vp, vp, C.c_int64, vp, i64p]
     L.srw_w2v_save_words.argtypes = [C.POINTER(C.c_char_p), f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
     L.srw_w2v_huffman.argtypes = [C.POINTER(C.c_int64), C.c_int64, i32p, C.POINTER(C.c_uint8), i32p]
     L.srw_w2v_save.argtypes = [i32p, f32p, C.c_int64, C.c_int32, C.c_char_p, C.c_int32]
@@ -903,6 +912,101 @@ class Engine:
                 n_win += int(pos.shape[0])
             means.append(loss_sum / max(n_win, 1))
         return emb_in, emb_out, means
+
+    # ---- asking a table of vectors: the k nearest rows (srw_topk_rows, srw_vertex_rows) ----
+    def _topk_args(self, what, table, rows, vectors):
+        """The tensor checks of topk_rows, in _sgns_args' order: TypeError before the library is called -> (Q, n, D, device)."""
+        is_t = lambda x: hasattr(x, "data_ptr") and hasattr(x, "is_cuda")      # noqa: E731
+        if rows is None and vectors is None:
+            raise TypeError("%s: at least one of rows and vectors is required" % what)
+        ids = [("rows", rows)] if rows is not None else []
+        tabs = [("table", table)] + ([("vectors", vectors)] if vectors is not None else [])
+        for name, t in ids + tabs:
+            if not is_t(t):
+                raise TypeError("%s: %s must be a torch tensor" % (what, name))
+        # (shape, contiguity and dtype first, the device last — skipgram's order: each refusal can be met without a GPU)
+        if table.dim() != 2:
+            raise TypeError("%s: table must be [n, D] (got %s)" % (what, tuple(table.shape)))
+        if vectors is not None and (vectors.dim() != 2 or vectors.shape[1] != table.shape[1]):
+            raise TypeError("%s: vectors must be [Q, D] with the table's D (got %s for a table %s)"
+                            % (what, tuple(vectors.shape), tuple(table.shape)))
+        if rows is not None and (rows.dim() != 1 or (vectors is not None and rows.shape[0] != vectors.shape[0])):
+            raise TypeError("%s: rows must be [Q] (got %s%s)"
+                            % (what, tuple(rows.shape), "" if vectors is None else " for vectors %s" % (tuple(vectors.shape),)))
+        for name, t in ids + tabs:
+            if not t.is_contiguous():
+                raise TypeError("%s: %s must be contiguous" % (what, name))
+        for name, t in ids:
+            if str(t.dtype) != "torch.int32":
+                raise TypeError("%s: %s must be torch.int32 (got %s)" % (what, name, t.dtype))
+        for name, t in tabs:
+            if str(t.dtype) != "torch.float32":
+                raise TypeError("%s: %s must be torch.float32 (got %s)" % (what, name, t.dtype))
+        mine = getattr(self, "device", None)
+        for name, t in ids + tabs:
+            if not t.is_cuda:
+                raise TypeError("%s: %s must be in device memory (got %s)" % (what, name, t.device))
+            if t.device != (ids + tabs)[0][1].device or (mine is not None and t.device.index != mine):
+                raise TypeError("%s: the tensors must be on the handle's device (cuda:%s), got %s for %s" % (what, mine, t.device, name))
+        Q = int(rows.shape[0]) if rows is not None else int(vectors.shape[0])
+        return Q, int(table.shape[0]), int(table.shape[1]), table.device
+
+    def topk_rows(self, table, k, rows=None, vectors=None, metric="cosine"):
+        """The k nearest rows of table (float32 [n, D] on the handle's device, D up to 1024, k up to 64) for every query, by
+        metric="cosine" or "dot", without forming the Q x n scores.  rows (int32 [Q]): query i is table[rows[i]], and that row is left
+        out of its own result; vectors (float32 [Q, D]): query i is vectors[i]; both: the vector is the query, rows[i] is left out
+        (-1: none).  A rows[i] that is no row of the table skips the query.  Returns (rows int32 [Q, k], scores float32 [Q, k],
+        n_skipped): best first by (score descending, row ascending); a result with fewer than k eligible rows, and every skipped
+        query's, ends in padding (row -1, score -inf).  Arithmetic and order: include/stellar_rw.h.  Tensor checks raise TypeError
+        before the library is called; the synchronisation rule is sgns_step's (torch's stream is waited for, the call is complete on
+        return)."""
+        import torch
+        Q, n, D, dev = self._topk_args("topk_rows", table, rows, vectors)
+        if metric not in TOPK_METRICS:
+            raise ValueError("topk_rows: metric must be 'cosine' or 'dot' (got %r)" % (metric,))
+        tp = TopkParams(D, int(k), TOPK_METRICS[metric], 0)
+        out_rows = torch.empty((Q, max(tp.k, 0)), dtype=torch.int32, device=dev)
+        out_scores = torch.empty((Q, max(tp.k, 0)), dtype=torch.float32, device=dev)
+        skipped = C.c_int64(0)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())          # noqa: E731
+        torch.cuda.current_stream(dev).synchronize()                     # the tensors are written before the handle's stream reads them
+        self._ck(lib().srw_topk_rows(self.h, ptr(table), n, ptr(vectors), ptr(rows), Q, C.byref(tp), ptr(out_rows), ptr(out_scores),
+                                     C.byref(skipped)))
+        return out_rows, out_scores, skipped.value
+
+    def rows_of(self, ids, return_unknown=False):
+        """The rows of vertex ids in a table laid out like vertices(): an int32 tensor on the handle's device, -1 for an id that is no
+        vertex of the graph.  ids: an int32 tensor [n] on the handle's device, or a list / numpy array of ids, which is uploaded.
+        return_unknown=True: (rows, the number of unknown ids)."""
+        import torch
+        if not (hasattr(ids, "data_ptr") and hasattr(ids, "is_cuda")):
+            dev = torch.device("cuda", getattr(self, "device", None) or 0)
+            ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int32)).to(dev)
+        if ids.dim() != 1 or not ids.is_contiguous() or str(ids.dtype) != "torch.int32":
+            raise TypeError("rows_of: ids must be a contiguous one-dimensional torch.int32 tensor (got %s, %s)" % (tuple(ids.shape), ids.dtype))
+        mine = getattr(self, "device", None)
+        if not ids.is_cuda or (mine is not None and ids.device.index != mine):
+            raise TypeError("rows_of: ids must be on the handle's device (cuda:%s), got %s" % (mine, ids.device))
+        out = torch.empty_like(ids)
+        unknown = C.c_int64(0)
+        torch.cuda.current_stream(ids.device).synchronize()              # the ids are written before the handle's stream reads them
+        self._ck(lib().srw_vertex_rows(self.h, C.c_void_p(ids.data_ptr()), int(ids.numel()), C.c_void_p(out.data_ptr()), C.byref(unknown)))
+        return (out, unknown.value) if return_unknown else out
+
+    def most_similar(self, emb, ids, k=10, metric="cosine"):
+        """findSynonyms for a table in the order of vertices() (train_sgns' emb_in): for every vertex id in ids its k nearest other
+        vertices -> (neighbour_ids int32 [Q, k], scores float32 [Q, k]), best first.  It is rows_of(ids), topk_rows(emb, k, rows=...)
+        and a device gather through vertices(); padding stays -1 / -inf, and an id that is no vertex gives a row of padding.
+        w2v_fit / w2v_fit_device return (vocab_ids, vectors) in VOCABULARY order instead; there the row of a word is its index in
+        vocab_ids:  t = torch.as_tensor(vectors).cuda(); r, s, _ = e.topk_rows(t, k, rows=torch.tensor([row_of_word], dtype=torch.int32,
+        device="cuda")); vocab_ids[r.cpu()] are the neighbours."""
+        import torch
+        rows = self.rows_of(ids)
+        r, scores, _ = self.topk_rows(emb, k, rows=rows, metric=metric)
+        V = torch.as_tensor(self.vertices(), dtype=torch.int32).to(r.device)
+        if V.numel() == 0:
+            return torch.full_like(r, -1), scores
+        return torch.where(r >= 0, V[r.clamp(min=0).long()], torch.full_like(r, -1)), scores
 
     def write_paths(self, output_dir, n_parts=1, write_crc=False):
         self._ck(lib().srw_write_paths(self.h, os.fsencode(output_dir), n_parts, int(write_crc)))

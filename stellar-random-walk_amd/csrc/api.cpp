@@ -791,6 +791,54 @@ int32_t srw_sgns_step(srw_handle *h, const void *d_pos, const void *d_neg, int64
   });
 }
 
+int32_t srw_topk_rows(srw_handle *h, const void *d_table, int64_t n_rows, const void *d_qvec, const void *d_qrow, int64_t n_queries,
+                      const srw_topk_params *tp, void *d_rows, void *d_scores, int64_t *n_skipped) {
+  if (!h || !tp) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need(tp->dim >= 1 && tp->dim <= 1024, "srw_topk_rows: dim must be in 1 .. 1024");
+    need(tp->k >= 1 && tp->k <= 64, "srw_topk_rows: k must be in 1 .. 64 (one list entry per lane of a wave)");
+    need(tp->metric == 0 || tp->metric == 1, "srw_topk_rows: metric must be 0 (cosine) or 1 (dot)");
+    need(tp->reserved == 0, "srw_topk_rows: reserved != 0");
+    need(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "srw_topk_rows: n_rows must be in [0, 2^31)");
+    need(n_queries >= 0, "srw_topk_rows: n_queries < 0");
+    if (n_queries == 0) { if (n_skipped) *n_skipped = 0; return; }     // an empty tensor's pointers are arbitrary; nothing to launch
+    need(d_table || n_rows == 0, "srw_topk_rows: d_table is null");
+    need(d_rows && d_scores, "srw_topk_rows: one of d_rows / d_scores is null");
+    need(d_qvec || d_qrow, "srw_topk_rows: neither d_qvec nor d_qrow is given");
+    need((((uintptr_t)d_table | (uintptr_t)d_qvec | (uintptr_t)d_qrow | (uintptr_t)d_rows | (uintptr_t)d_scores) & 3u) == 0,
+         "srw_topk_rows: a pointer is not aligned to 4 bytes");
+    need(n_queries <= (((int64_t)1 << 62) / 4) / ((int64_t)tp->dim * 64), "srw_topk_rows: n_queries is too large");   // (the byte counts below fit)
+    const uintptr_t out_b = (uintptr_t)n_queries * (uintptr_t)tp->k * 4u;
+    const struct { uintptr_t p, bytes; } in[3] = {{(uintptr_t)d_table, (uintptr_t)n_rows * (uintptr_t)tp->dim * 4u},
+                                                  {(uintptr_t)d_qvec, (uintptr_t)n_queries * (uintptr_t)tp->dim * 4u},
+                                                  {(uintptr_t)d_qrow, (uintptr_t)n_queries * 4u}};
+    const uintptr_t out[2] = {(uintptr_t)d_rows, (uintptr_t)d_scores};
+    need(out[0] + out_b <= out[1] || out[1] + out_b <= out[0], "srw_topk_rows: d_rows and d_scores overlap");
+    for (int o = 0; o < 2; ++o)
+      for (int i = 0; i < 3; ++i)
+        need(!in[i].p || in[i].bytes == 0 || out[o] + out_b <= in[i].p || in[i].p + in[i].bytes <= out[o],
+             "srw_topk_rows: an output overlaps an input");
+    const int64_t skipped = topk_rows(h, (const float *)d_table, n_rows, (const float *)d_qvec, (const int32_t *)d_qrow, n_queries, *tp,
+                                      (int32_t *)d_rows, (float *)d_scores);
+    if (n_skipped) *n_skipped = skipped;
+  });
+}
+
+int32_t srw_vertex_rows(srw_handle *h, const void *d_ids, int64_t n, void *d_rows, int64_t *n_unknown) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_single_gpu(h, "srw_vertex_rows");
+    need(h->g.loaded, "srw_vertex_rows: no graph loaded");
+    need(n >= 0, "srw_vertex_rows: n < 0");
+    if (n == 0) { if (n_unknown) *n_unknown = 0; return; }
+    need(d_ids && d_rows, "srw_vertex_rows: one of d_ids / d_rows is null");
+    need((((uintptr_t)d_ids | (uintptr_t)d_rows) & 3u) == 0, "srw_vertex_rows: a pointer is not aligned to 4 bytes");
+    need(n < ((int64_t)1 << 39), "srw_vertex_rows: n is too large");
+    const int64_t unknown = vertex_rows(h, (const int32_t *)d_ids, n, (int32_t *)d_rows);
+    if (n_unknown) *n_unknown = unknown;
+  });
+}
+
 int32_t srw_w2v_huffman(const int64_t *counts, int64_t n_vocab, int32_t *code_len, uint8_t *codes, int32_t *points) {
   if (!counts || !code_len || !codes || !points || n_vocab < 0) return SRW_ERR_INVALID;
   try { w2v_huffman(counts, n_vocab, code_len, codes, points); return SRW_OK; }

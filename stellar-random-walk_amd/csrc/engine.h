@@ -196,7 +196,8 @@ struct srw_handle {
   srw::DevBuf<int64_t> sg_off;                   // srw_skipgram_windows: first window of every row [n + 1] ...
   srw::DevBuf<char> sg_temp;                     // ... and rocprim's temporary storage (both kept between calls: one call per training step)
   srw::DevBuf<unsigned long long> vc_slots;      // srw_path_vertex_counts: occurrences per slot [n_slots], then the ids that are no vertex [1]
-  srw::DevBuf<unsigned long long> sgns_skipped;  // srw_sgns_step: windows skipped for an id that is no present vertex [1]
+  srw::DevBuf<unsigned long long> sgns_skipped;  // srw_sgns_step: windows skipped for an id that is no present vertex [1]; srw_vertex_rows: ids that are no vertex
+  srw::DevBuf<char> topk_scratch;                // srw_topk_rows: one pass's candidate lists, staged queries and the skip count (topk.hip)
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
   // srw_cluster_set_sources: the entries of the cluster's list that THIS shard owns, in list order (shard_set_sources, sources.hip):
@@ -311,6 +312,15 @@ bool load_edgelist_device(srw_handle *h, const char *path, bool directed, bool w
 // stream, complete on return -> windows skipped for an id that is no present vertex
 int64_t sgns_step(srw_handle *h, const int32_t *d_pos, const int32_t *d_neg, int64_t n_windows, const srw_sgns_params &sp,
                   const float *d_in, const float *d_out, float *d_in_new, float *d_out_new, float *d_loss);
+// g.vpos: slot -> position in V, built once per graph on the handle's stream (a load drops it with the graph)
+void ensure_vpos(srw_handle *h);
+
+// ---- topk.hip ----
+// srw_topk_rows / srw_vertex_rows behind their argument checks (api.cpp), on the handle's stream, complete on return -> queries skipped /
+// ids that are no vertex
+int64_t topk_rows(srw_handle *h, const float *d_table, int64_t n_rows, const float *d_qvec, const int32_t *d_qrow, int64_t n_queries,
+                  const srw_topk_params &tp, int32_t *d_rows, float *d_scores);
+int64_t vertex_rows(srw_handle *h, const int32_t *d_ids, int64_t n, int32_t *d_rows);
 
 // ---- sources.hip ----
 // The list of start vertices of the next walks: h_ids (host) or d_ids (on the handle's device), n entries.  Throws SRW_ERR_INVALID and

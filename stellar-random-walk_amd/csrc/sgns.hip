@@ -149,7 +149,7 @@ void launch_sgns(srw_handle *h, const SgnsArgs &a) {
 }  // namespace
 
 // slot -> position in V, once per graph (a load drops it with the graph)
-static void ensure_vpos(srw_handle *h) {
+void ensure_vpos(srw_handle *h) {
   Graph &g = h->g;
   if (g.has_vpos) return;
   g.vpos.alloc((size_t)g.n_slots);
