@@ -179,7 +179,7 @@ typedef struct {
   int64_t fallbacks;    /* steps that needed the exact sequential fallback */
   int64_t trials;       /* Mode A: alias draws (accepted + rejected) */
   double kernel_ms;     /* hipEvent time of the walk kernels of this call, on the handle's stream */
-  int32_t kernel_kind;  /* 1 = first-order guide-table kernel, 2 = general second-order kernel, 3 = alias */
+  int32_t kernel_kind;  /* 1 = first-order guide-table kernel, 2 = general second-order kernel, 3 = alias, 4 = metapath */
   int32_t record_bytes; /* bytes of one sampling-table record read by this kernel (16 compact / 32 / 0) */
   int64_t strategy_steps[12]; /* general kernel: steps served by each sampler, indexed by SRW_STRAT_* */
   int64_t edge_tables;       /* per-edge bias tables in use by this call (0: none built) */
@@ -245,6 +245,46 @@ int32_t srw_set_sources_device(srw_handle *h, const void *d_ids, int64_t n);
 int32_t srw_clear_sources(srw_handle *h);
 /* *n = length of the list in force, -1 when there is none (walks start from every vertex). */
 int32_t srw_sources(const srw_handle *h, int64_t *n);
+
+/* ---- metapath walks: steps restricted to vertex types (whole-graph handles) ------------
+ * No reference counterpart (the reference walks homogeneous graphs); the semantics are those of StellarGraph's
+ * UniformRandomMetaPathWalk and PyG's MetaPath2Vec, with RandomSample.sample as the draw: the vertex at path position j must
+ * have the type the pattern names for j.
+ *
+ * Vertex types.  One uint8 per present vertex, indexed by position in V, the ascending list srw_graph_vertices returns (as the
+ * negative weights and the SGNS tables are).  d_types: n bytes in device memory on the handle's GPU; the bytes are copied on the
+ * handle's stream (with them the type of every adjacency entry's vertex is laid out beside the rows, 1 byte per entry), the call
+ * is complete on return.  d_types == NULL clears the types (n is ignored).  Loading a graph drops them.  SRW_ERR_INVALID, with
+ * the previous types left in force: no graph loaded, n != nV, a NULL h, a sharded handle (world > 1), population 1 selected.
+ * SRW_ERR_NOMEM, likewise with the previous types in force, when the per-entry bytes do not fit: the walk has no other sampler. */
+int32_t srw_vertex_types_set(srw_handle *h, const void *d_types, int64_t n);
+/* *n = nV when types are in force, -1 when there are none. */
+int32_t srw_vertex_types(const srw_handle *h, int64_t *n);
+/* The walk.  pattern[m] (host), 1 <= m <= 64, each entry in 0 .. 255 (a type) or -1 (any type).  Path position j (j = 0 is the
+ * source) has the required type pattern[j mod m]: StellarGraph's metapath [a, p, a] is pattern = {a, p}.  Walkers, iterations,
+ * first_walk, the start list of srw_set_sources and the result buffers are exactly srw_walk's: int32 [n_walkers][walk_length + 2]
+ * with tail -1, plus lens.  The result replaces the handle's last walk result: srw_fetch_paths, srw_device_paths, srw_write_paths,
+ * srw_skipgram_windows / _batch, srw_path_vertex_counts and srw_w2v_fit_device with NULL pointers then act on it.
+ * A source whose type does not match pattern[0] yields the one-entry path [src].  Step s = 1 .. walk_length + 1:
+ *   u           the very draw srw_walk uses for step s of that walker: draw_uniform(rng, iteration, source id as the input spelled
+ *               it, s) — the Philox stream above, or const_r under SRW_RNG_CONST.
+ *   candidates  the entries of N(curr) IN ROW ORDER whose vertex matches pattern[s mod m]; multi-edges and self-loops are kept (a
+ *               self-loop's type is curr's own).  With no such entry (an empty row included) the walk ends.
+ *   next        RandomSample.sample (M/algorithm/RandomSample.scala:12-25) applied to THAT SUBLIST with its raw weights: S = the
+ *               f64 left fold of the sublist's weights, acc += (double)w / S entry by entry, the answer is the first entry with
+ *               acc >= (double)u, and the sublist's HEAD if there is none.  An entry that does not match is no candidate — it is
+ *               not a candidate of weight zero: it can be neither the first acc >= u (u = 0) nor the head.
+ * The step is first-order only: p and q must both be 1.0f.
+ * Two consequences: with pattern = {-1} the result is bit for bit srw_walk's with p = q = 1, for any types and any rng mode; and
+ * so it is with every vertex of type t and pattern = {t}.
+ * stats: n_walkers; n_steps = sum of (len - 1); dead_ends = walkers that stopped at a step s > 1 (the general kernel's rule: a
+ * source of the wrong type or without a candidate at s = 1 is not counted); fallbacks = steps decided by the exact sequential
+ * chain; kernel_ms; kernel_kind = 4; everything else 0.
+ * SRW_ERR_INVALID before any launch, the previous walk result intact: a NULL h, params or pattern; no graph; a sharded handle
+ * (world > 1); population 1 selected; no types in force (even for an all-wildcard pattern); m outside 1 .. 64; an entry outside
+ * -1 .. 255; p != 1 or q != 1; sampler != SRW_SAMPLER_REFERENCE; whatever srw_walk refuses in walk_length, num_walks or rng_mode.
+ * params->flags is ignored. */
+int32_t srw_walk_metapath(srw_handle *h, const srw_walk_params *params, const int32_t *pattern, int32_t m, srw_walk_stats *stats);
 
 /* Pinned (page-locked) host memory for srw_walk_to_host / srw_fetch_paths destinations. */
 int32_t srw_host_alloc(size_t bytes, void **out);

@@ -109,7 +109,7 @@ STRATEGIES = ("edge_table", "p1", "p2", "w", "p3", "scan", "prefix", "chain", "e
 EXPORTS = [
     "srw_create", "srw_destroy", "srw_last_error", "srw_set_stream", "srw_plan_walks", "srw_load_edgelist", "srw_load_coo", "srw_load_coo_device",
     "srw_load_adjacency", "srw_generate_rmat", "srw_graph_stats", "srw_graph_vertices", "srw_graph_neighbors",
-    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
+    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_vertex_types_set", "srw_vertex_types", "srw_walk_metapath", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
     "srw_shard_capacity", "srw_shard_vertex_ranks", "srw_shard_layout_for", "srw_shard_begin", "srw_shard_superstep",
     "srw_shard_flush", "srw_shard_finish", "srw_shard_rows_count", "srw_shard_rows_export", "srw_shard_rows_merge",
     "srw_shard_rows_commit", "srw_shard_rows_release", "srw_device_alloc", "srw_device_free", "srw_cluster_create", "srw_cluster_destroy", "srw_cluster_last_error",
@@ -158,6 +158,9 @@ def lib():
     L.srw_set_sources_device.argtypes = [vp, vp, C.c_int64]
     L.srw_clear_sources.argtypes = [vp]
     L.srw_sources.argtypes = [vp, i64p]
+    L.srw_vertex_types_set.argtypes = [vp, vp, C.c_int64]
+    L.srw_vertex_types.argtypes = [vp, i64p]
+    L.srw_walk_metapath.argtypes = [vp, C.POINTER(WalkParams), i32p, C.c_int32, C.POINTER(WalkStats)]
     L.srw_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.srw_host_free.argtypes = [vp]
     L.srw_host_free.restype = None
@@ -559,6 +562,83 @@ class Engine:
         P = self.params(**kw)
         st = WalkStats()
         self._ck(lib().srw_walk(self.h, C.byref(P), C.byref(st)))
+        if not fetch:
+            return st.as_dict()
+        paths = np.empty((max(st.n_walkers, 1), P.walk_length + 2), dtype=np.int32)
+        lens = np.empty(max(st.n_walkers, 1), dtype=np.int32)
+        self._ck(lib().srw_fetch_paths(self.h, _i32(paths), _i32(lens)))
+        return paths[:st.n_walkers], lens[:st.n_walkers], st.as_dict()
+
+    # ---- metapath walks: steps restricted to vertex types (srw_vertex_types_set / srw_walk_metapath) ----
+    def set_vertex_types(self, types):
+        """One type (0 .. 255) per present vertex, indexed like vertices(): a torch.uint8 tensor [nV], contiguous, on the handle's
+        device, or a list / numpy array of integers in 0 .. 255, which is uploaded.  None clears.  The types last until the next load.
+        A wrong dtype, shape, device or range is a TypeError before the library is called; a wrong length is the library's refusal."""
+        if types is None:
+            self._ck(lib().srw_vertex_types_set(self.h, None, 0))
+            return self
+        import torch
+        mine = getattr(self, "device", None)
+        if hasattr(types, "data_ptr") and hasattr(types, "is_cuda"):
+            t = types
+            # (shape, contiguity and dtype first, the device last — skipgram's order: each refusal can be met without a GPU)
+            if t.dim() != 1:
+                raise TypeError("set_vertex_types: types must be one-dimensional [nV] (got %s)" % (tuple(t.shape),))
+            if not t.is_contiguous():
+                raise TypeError("set_vertex_types: types must be contiguous")
+            if str(t.dtype) != "torch.uint8":
+                raise TypeError("set_vertex_types: a tensor of types must be torch.uint8 (got %s)" % t.dtype)
+            if not t.is_cuda:
+                raise TypeError("set_vertex_types: a tensor of types must be in device memory (got %s)" % t.device)
+            if mine is not None and t.device.index != mine:
+                raise TypeError("set_vertex_types: the tensor must be on the handle's device (cuda:%s), got %s" % (mine, t.device))
+        else:
+            a = np.asarray(types)
+            if a.ndim != 1:
+                raise TypeError("set_vertex_types: types must be one-dimensional [nV] (got %s)" % (a.shape,))
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError("set_vertex_types: types must be integers (got %s)" % a.dtype)
+            if a.size and (int(a.min()) < 0 or int(a.max()) > 255):
+                raise TypeError("set_vertex_types: a type is outside the range 0 .. 255")
+            t = torch.as_tensor(np.array(a, dtype=np.uint8)).to(torch.device("cuda", mine or 0))
+        n = int(t.numel())
+        if not n:
+            t = torch.zeros(1, dtype=torch.uint8, device=t.device)       # (a pointer that is not NULL: NULL clears)
+        torch.cuda.current_stream(t.device).synchronize()                # the types are written before the handle's stream reads them
+        self._ck(lib().srw_vertex_types_set(self.h, C.c_void_p(t.data_ptr()), n))
+        return self
+
+    def vertex_types_len(self):
+        """nV when vertex types are in force, -1 when there are none."""
+        n = C.c_int64(0)
+        self._ck(lib().srw_vertex_types(self.h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def _metapath_pattern(pattern):
+        """walk_metapath's pattern as int32 [m]; TypeError before the library is called."""
+        if isinstance(pattern, (str, bytes)) or not hasattr(pattern, "__len__"):
+            raise TypeError("walk_metapath: pattern must be a sequence of integers (got %s)" % type(pattern).__name__)
+        a = np.asarray(pattern)
+        if a.ndim != 1 or not 1 <= a.size <= 64:
+            raise TypeError("walk_metapath: pattern must have 1 .. 64 entries (got shape %s)" % (a.shape,))
+        if a.dtype.kind not in "iu":
+            raise TypeError("walk_metapath: pattern entries must be integers (got %s)" % a.dtype)
+        if int(a.min()) < -1 or int(a.max()) > 255:
+            raise TypeError("walk_metapath: a pattern entry is outside -1 .. 255 (a type, or -1 for any)")
+        return np.array(a, dtype=np.int32)
+
+    def walk_metapath(self, pattern, fetch=True, sources=None, **kw):
+        """Runs srw_walk_metapath: the vertex at path position j has the type pattern[j mod m] (-1: any type); StellarGraph's metapath
+        [a, p, a] is pattern=[a, p].  Needs set_vertex_types.  Returns what walk returns, and the result replaces the last walk's:
+        paths_tensor, skipgram, skipgram_batch, visit_counts, write_paths and w2v_fit_device then act on it.  kw as params (p and q
+        must stay 1, the sampler the reference one); sources as in walk.  A source of the wrong type gives the one-entry path."""
+        pat = self._metapath_pattern(pattern)
+        if sources is not None:
+            return self._with_sources(sources, lambda: self.walk_metapath(pat, fetch=fetch, **kw))
+        P = self.params(**kw)
+        st = WalkStats()
+        self._ck(lib().srw_walk_metapath(self.h, C.byref(P), _i32(pat), int(pat.size), C.byref(st)))
         if not fetch:
             return st.as_dict()
         paths = np.empty((max(st.n_walkers, 1), P.walk_length + 2), dtype=np.int32)

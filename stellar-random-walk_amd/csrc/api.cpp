@@ -439,6 +439,41 @@ int32_t srw_sources(const srw_handle *h, int64_t *n) {
   return SRW_OK;
 }
 
+// ---- metapath walks (metapath.hip) ----
+int32_t srw_vertex_types_set(srw_handle *h, const void *d_types, int64_t n) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_vertex_types_set");
+    if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_vertex_types_set needs a whole-graph handle (world == 1)");
+    if (!d_types) { vertex_types_clear(h); return; }
+    need(h->g.loaded, "srw_vertex_types_set: no graph loaded");
+    if (n != h->g.n_vertices)
+      throw Error(SRW_ERR_INVALID, "srw_vertex_types_set: n = " + std::to_string(n) + " types for " + std::to_string(h->g.n_vertices) + " vertices");
+    try { vertex_types_set(h, (const uint8_t *)d_types, n); }
+    catch (const Error &e) { throw Error(e.code, std::string("srw_vertex_types_set: ") + e.what()); }
+  });
+}
+
+int32_t srw_vertex_types(const srw_handle *h, int64_t *n) {
+  if (!h || !n) return SRW_ERR_INVALID;
+  *n = h->g.has_types ? h->g.n_vertices : -1;
+  return SRW_OK;
+}
+
+int32_t srw_walk_metapath(srw_handle *h, const srw_walk_params *params, const int32_t *pattern, int32_t m, srw_walk_stats *stats) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_walk_metapath");
+    need(params != nullptr, "srw_walk_metapath: params is null");
+    need(pattern != nullptr, "srw_walk_metapath: pattern is null");
+    try { run_walk_metapath(h, *params, pattern, m, stats); }
+    catch (const Error &e) {
+      if (std::string(e.what()).rfind("srw_walk_metapath", 0) == 0) throw;
+      throw Error(e.code, std::string("srw_walk_metapath: ") + e.what());
+    }
+  });
+}
+
 int32_t srw_host_alloc(size_t bytes, void **out) {
   if (!out) return SRW_ERR_INVALID;
   *out = nullptr;

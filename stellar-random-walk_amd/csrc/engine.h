@@ -142,6 +142,11 @@ struct Graph {
   // srw_sgns_step (sgns.hip): position in V of every slot's vertex, -1 for a slot that is no present vertex; built at the first step
   DevBuf<int32_t> vpos;           // [n_slots]
   bool has_vpos = false;
+  // srw_vertex_types_set (metapath.hip): the type of every present vertex over verts[] and, built from it, the type of every adjacency
+  // entry's vertex (what k_walk_metapath streams beside a row); a load drops both with the graph
+  DevBuf<uint8_t> vtypes;         // [n_vertices]
+  DevBuf<uint8_t> etype;          // [n_entries]
+  bool has_types = false;
   std::vector<int32_t> part_of;   // VCut: last pId recorded per dst slot, -1 none (host side; empty if unused)
   GraphView view() const { return GraphView{rows.p, ent.p, sids.p, sperm.p, has_fo ? fo.p : nullptr, (has_cfo || cfo_linked || has_cfo_local) ? cfo.p : nullptr, has_al ? al.p : nullptr, has_al ? rsum.p : nullptr,
                      mrows.p ? mrows.p : rows.p, msids.p ? msids.p : sids.p, (has_pq && pq_unit == 0.0) ? pq.p : nullptr, has_pq ? pq_ok.p : nullptr, (has_ehash && use_ehash) ? ehash.p : nullptr, ehash_mask,
@@ -353,6 +358,14 @@ int64_t path_vertex_counts(srw_handle *h, const int32_t *d_paths, const int32_t 
 // while they hit their own window when bp.exclude_window is set
 int64_t skipgram_batch(srw_handle *h, const int32_t *d_paths, const int32_t *d_lens, int64_t n, int64_t stride,
                        const srw_skipgram_batch_params &bp, int32_t *d_pos, int32_t *d_neg, int64_t cap_windows);
+
+// ---- metapath.hip ----
+// Behind their argument checks (api.cpp), on the handle's stream, complete on return.  vertex_types_set: d_types [n = n_vertices] bytes on
+// the handle's device -> the types in force and the per-entry bytes; an allocation that fails leaves the previous types in force.
+void vertex_types_set(srw_handle *h, const uint8_t *d_types, int64_t n);
+void vertex_types_clear(srw_handle *h);
+// srw_walk_metapath: every refusal comes before a launch or a change of the handle's walk result
+void run_walk_metapath(srw_handle *h, const srw_walk_params &P, const int32_t *pattern, int32_t m, srw_walk_stats *stats);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);
