@@ -642,6 +642,13 @@ int32_t srw_second_order_sample(srw_handle *h, float p, float q, int32_t prev_id
 /* The walk RNG stream evaluated on the GPU: out[i] = u(seed, iter[i], src[i], step[i]). */
 int32_t srw_rng_uniform(srw_handle *h, uint32_t seed, const uint32_t *iter, const uint32_t *src,
                         const uint32_t *step, int64_t n, float *out);
+/* The first-order pick through the 16-byte compact records (csrc/sampling.h:cfo_pick, what a p = q = 1 Philox walk does at every step)
+ * on the row of `vertex`, one draw per element: m[i] < 2^24 is the lattice draw (p = m[i] * 2^-24), pos[i] the picked position inside
+ * the row — RandomSample.sample's index for that p — and reads[i] the 16-byte records the pick loaded (1 where the guide entry's own
+ * record is the answer).  Builds the compact table if the handle has none yet.  SRW_ERR_INVALID: no graph, a sharded handle, a
+ * vertex that is absent / without neighbours / irregular (a negative or NaN weight), a draw >= 2^24, a graph whose compact table had
+ * to be abandoned (a neighbour row too long for a link).  No reference counterpart: the reference scans the row. */
+int32_t srw_cfo_pick(srw_handle *h, int32_t vertex, const uint32_t *m, int64_t n, int32_t *pos, int32_t *reads);
 
 /* ---- host-only helpers (no GPU needed) ------------------------------------------------------ */
 /* The edge-list tokenizer on its own: parses `path` into caller-visible arrays owned by the library

@@ -117,7 +117,7 @@ EXPORTS = [
     "srw_cluster_graph_stats", "srw_cluster_walk", "srw_cluster_fetch_paths", "srw_cluster_walk_and_save",
     "srw_cluster_set_sources", "srw_cluster_clear_sources", "srw_cluster_sources",
     "srw_shard_select", "srw_w2v_fit", "srw_w2v_fit_device", "srw_skipgram_windows", "srw_negative_weights_set", "srw_graph_degrees_device", "srw_path_vertex_counts", "srw_skipgram_batch", "srw_sgns_step", "srw_topk_rows", "srw_vertex_rows", "srw_w2v_huffman", "srw_w2v_save", "srw_w2v_save_words", "srw_probe_request_rate", "srw_result_scan_sums", "srw_sample", "srw_second_order_weights",
-    "srw_second_order_sample", "srw_rng_uniform", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
+    "srw_second_order_sample", "srw_rng_uniform", "srw_cfo_pick", "srw_parse_edgelist", "srw_parse_sources", "srw_free", "srw_save_paths", "srw_table_geometry", "srw_version",
 ]
 
 _lib = None
@@ -221,6 +221,7 @@ def lib():
     L.srw_second_order_sample.argtypes = [vp, C.c_float, C.c_float, C.c_int32, i32p, C.c_int64, i32p, f32p,
                                           C.c_int64, C.c_float, i64p]
     L.srw_rng_uniform.argtypes = [vp, C.c_uint32, u32p, u32p, u32p, C.c_int64, f32p]
+    L.srw_cfo_pick.argtypes = [vp, C.c_int32, u32p, C.c_int64, i32p, i32p]
     L.srw_parse_edgelist.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(i32p), C.POINTER(i32p),
                                      C.POINTER(f32p), C.POINTER(i32p), i64p, C.c_char_p, C.c_size_t]
     L.srw_parse_sources.argtypes = [C.c_char_p, C.POINTER(i32p), i64p, C.c_char_p, C.c_size_t]
@@ -1162,6 +1163,14 @@ class Engine:
         self._ck(lib().srw_rng_uniform(self.h, seed, it.ctypes.data_as(u32p), src.ctypes.data_as(u32p),
                                        step.ctypes.data_as(u32p), len(it), _f32(out)))
         return out
+
+    def cfo_pick(self, vertex, m):
+        """The compact-record pick (csrc/sampling.h:cfo_pick) on the row of `vertex` for the 24-bit lattice draws m (p = m * 2^-24):
+        (positions inside the row, 16-byte records each pick loaded).  Builds the compact first-order table if need be."""
+        m = np.ascontiguousarray(m, dtype=np.uint32)
+        pos = np.empty(len(m), dtype=np.int32); reads = np.empty(len(m), dtype=np.int32)
+        self._ck(lib().srw_cfo_pick(self.h, int(vertex), m.ctypes.data_as(C.POINTER(C.c_uint32)), len(m), _i32(pos), _i32(reads)))
+        return pos, reads
 
 
 def w2v_huffman(counts):

@@ -938,6 +938,16 @@ int32_t srw_rng_uniform(srw_handle *h, uint32_t seed, const uint32_t *iter, cons
   return guarded(h, [&] { need(iter && src && step && out, "null argument"); hook_rng(h, seed, iter, src, step, n, out); });
 }
 
+int32_t srw_cfo_pick(srw_handle *h, int32_t vertex, const uint32_t *m, int64_t n, int32_t *pos, int32_t *reads) {
+  if (!h) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_cfo_pick");
+    need(n >= 0, "srw_cfo_pick: n < 0");
+    need(n == 0 || (m && pos && reads), "null argument");
+    hook_cfo_pick(h, vertex, m, n, pos, reads);
+  });
+}
+
 int32_t srw_parse_edgelist(const char *path, int32_t weighted, int32_t partitioned, int32_t **src, int32_t **dst, float **w,
                            int32_t **pid, int64_t *n_lines, char *err, size_t errlen) {
   if (!path || !n_lines) return SRW_ERR_INVALID;

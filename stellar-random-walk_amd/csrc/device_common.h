@@ -53,8 +53,13 @@ struct alignas(32) FoEnt {
 //   id   : neighbor id
 //   link : bits 0..35 noff | bits 36..39 high 4 bits of the guide delta | bits 40..62 ndeg (< 2^23 - 1) |
 //          bit 63 next row needs the generic path
-// guide delta gd = j - guide[j] as a signed 12-bit number (-2047 .. 2047; weighted hub rows need both signs and
+// guide delta gd = j - guide[j] as a signed 12-bit number (-2047 .. 2046; weighted hub rows need both signs and
 // hundreds); CFO_GD_SAT marks an entry whose delta does not fit: the pick then searches the row's (monotone) c values.
+// CFO_GD_EDGE (bucket j >= 1 only) stands for a delta of 1 that only the bucket's LOWEST lattice draw needs: the builder writes
+// it when guide[j] == j - 1 and c[j - 1] == ceil(j * 2^24 / deg) exactly (sampler_tables.hip:cfo_write).  Every other draw m of
+// the bucket has m - 1 in the bucket too, so m > ceil(j * 2^24 / deg) = c[j - 1]: its first crossing is not before j, and the
+// record of j is the one already loaded.  That is every bucket of a unit-weight row whose threshold j * 2^24 / deg is an integer
+// (the f64 running sum can land exactly on it) — 4 % of the steps of an RMAT walk paid two more dependent loads for them.
 struct alignas(16) CfoEnt {
   uint32_t cg;
   int32_t id;
@@ -62,10 +67,28 @@ struct alignas(16) CfoEnt {
 };
 constexpr uint32_t CFO_NDEG_MAX = (1u << 23) - 2u;
 constexpr int32_t CFO_GD_SAT = -2048;
+constexpr int32_t CFO_GD_EDGE = 2047;
 constexpr uint64_t CFO_NOFF_MASK = (1ull << 36) - 1ull;
-__host__ __device__ inline int32_t cfo_delta(uint32_t cg, uint64_t link) {
+// the 12 stored bits, for the builder and for the two decoders below ONLY: no reader of a record acts on the raw code
+__host__ __device__ inline int32_t cfo_delta_code(uint32_t cg, uint64_t link) {
   const uint32_t d = (cg >> 24) | ((uint32_t)((link >> 36) & 0xFull) << 8);
   return (int32_t)(d << 20) >> 20;                     // sign-extend 12 bits
+}
+// the builder's side: the code of a guide delta; `edge` = the certificate above holds for this bucket
+__host__ __device__ inline int32_t cfo_delta_encode(int32_t delta, bool edge) {
+  if (edge && delta == 1) return CFO_GD_EDGE;
+  return (delta < -2047 || delta >= CFO_GD_EDGE) ? CFO_GD_SAT : delta;   // a genuine 2047 saturates: the pick bisects the row
+}
+// a lower-bound delta for ANY draw of the record's bucket (CFO_GD_SAT: none stored)
+__host__ __device__ inline int32_t cfo_delta(uint32_t cg, uint64_t link) {
+  const int32_t d = cfo_delta_code(cg, link);
+  return d == CFO_GD_EDGE ? 1 : d;
+}
+// ... and for the lattice draw m, which fell into bucket j of a row of deg entries: 0 under the edge code unless m is the bucket's lowest draw
+__host__ __device__ inline int32_t cfo_delta(uint32_t cg, uint64_t link, uint32_t j, uint32_t m, uint32_t deg) {
+  const int32_t d = cfo_delta_code(cg, link);
+  if (d != CFO_GD_EDGE) return d;
+  return (uint32_t)(((uint64_t)(m - 1u) * (uint64_t)deg) >> 24) < j ? 1 : 0;    // (j >= 1 under the code, so m >= 1)
 }
 
 // Mode A record: alias slot of entry k of a row + the neighbor's id / weight / row descriptor (linked).
@@ -149,6 +172,7 @@ struct GraphView {
   // ... and no prefix-sum array: the exact prefix of the base weights fl(1 / q) of a unit-weight row is (k + 1) * pq_unit (0: read pq)
   double pq_unit;
   int32_t dbg_chain_deg;   // tests (SRW_DEBUG_CHAIN_DEG): sharded steps on rows at least this long are treated as draws on a CDF boundary (0: off)
+  int32_t cfo_reload;      // A/B and tests (tables built under SRW_NO_EDGE_CODE): cfo_pick loads bucket j's record again when its scan comes back to it, as it did before CFO_GD_EDGE (0: off)
 };
 // The exact prefix sums PQ[k] of a row's base weights fl(w / q): the per-call array (8 B per entry) — or, on a unit-weight graph, the
 // closed form (k + 1) * fl(1 / q): k + 1 < 2^24 and a 24-bit constant, the product is exact and equals the sum of k + 1 copies.

@@ -86,6 +86,7 @@ struct Graph {
   DevBuf<CfoEnt> cfo;             // [n_entries] compact lattice records (optional)
   bool has_cfo = false;
   bool cfo_rejected = false;      // the compact table was tried and some entry needed an escape
+  bool cfo_plain = false;         // cfo was built under SRW_NO_EDGE_CODE: plain guide deltas, and the pick loads as it did before the code (GraphView::cfo_reload)
   DevBuf<Row> rows_all;           // vertex-sharded walk: every vertex's row descriptor as its OWNER stores it (srw_shard_rows_*)
   bool cfo_linked = false;        // cfo holds records whose links point into the owners' tables (k_sh_step_cfo only)
   DevBuf<AEnt> al;                // [n_entries] Mode A alias records, built lazily
@@ -155,7 +156,7 @@ struct Graph {
                      (has_eb && use_eb && !eb_sharded) ? eb_off.p : nullptr, eb_bins.p, eb_min_sh, em_bits.p, eb_mask_max, eb_f32,
                      has_rev ? rev.p : nullptr, eb_cap, compact ? orig_id.p : nullptr,
                      (has_bf && use_eb && !(has_ehash && use_ehash)) ? bf_off.p : nullptr, bf_bits.p,
-                     (has_eb && use_eb && eb_sharded) ? ph.p : nullptr, ph_buckets, has_rh ? rh.p : nullptr, rh_buckets, ebp, has_ids32 ? ids32.p : nullptr, (has_pq && pq_unit != 0.0) ? pq_unit : 0.0, dbg_chain_deg}; }
+                     (has_eb && use_eb && eb_sharded) ? ph.p : nullptr, ph_buckets, has_rh ? rh.p : nullptr, rh_buckets, ebp, has_ids32 ? ids32.p : nullptr, (has_pq && pq_unit != 0.0) ? pq_unit : 0.0, dbg_chain_deg, cfo_plain ? 1 : 0}; }
   // id <-> slot at the boundary (api.cpp): -1 if the id cannot be a vertex of this graph
   int64_t slot_of_id(int32_t v) const {
     if (!compact) { const int64_t s = (int64_t)v - vmin; return (s < 0 || s >= n_slots) ? -1 : s; }
@@ -478,5 +479,6 @@ void hook_second_order(srw_handle *h, float p, float q, int32_t prev_id, const i
                        int64_t *index);
 void hook_rng(srw_handle *h, uint32_t seed, const uint32_t *iter, const uint32_t *src, const uint32_t *step,
               int64_t n, float *out);
+void hook_cfo_pick(srw_handle *h, int32_t vertex, const uint32_t *m, int64_t n, int32_t *pos, int32_t *reads);
 
 }  // namespace srw

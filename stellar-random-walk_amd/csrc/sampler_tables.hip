@@ -254,8 +254,8 @@ __global__ void k_fo_link(const Row *__restrict__ rows, FoEnt *__restrict__ fo, 
 // ---- compact 16-byte records (lattice draws) derived from the CDF / guide store ------------------------------------
 template <class ST>
 __device__ inline void cfo_write(const ST &st, const Row *__restrict__ rows /* of the neighbors: the links */, const Ent *__restrict__ ent, int32_t vmin,
-                                 int64_t n_slots, const Row &r, int32_t j, bool regular, CfoEnt *__restrict__ cfo,
-                                 unsigned long long *escapes) {
+                                 int64_t n_slots, const Row &r, int32_t j, bool regular, bool edge_code,
+                                 CfoEnt *__restrict__ cfo, unsigned long long *escapes) {
   const int64_t e = r.off + j;
   const int32_t id = ent[e].id;
   const int64_t s = (int64_t)id - vmin;
@@ -267,7 +267,15 @@ __device__ inline void cfo_write(const ST &st, const Row *__restrict__ rows /* o
     const double sc = st.cdf(e) * 16777216.0;                     // exact scaling
     const uint32_t c = sc >= 16777215.0 ? 16777215u : (uint32_t)sc;   // min(floor, 2^24 - 1); cdf >= 0 on a regular row
     const int32_t delta = j - st.guide(e);
-    const int32_t d12 = (delta < -2047 || delta > 2047) ? CFO_GD_SAT : delta;   // saturated: the pick bisects the row
+    // CFO_GD_EDGE's certificate (device_common.h): the guide is j - 1 and the predecessor's stored c IS the bucket's threshold (the guide
+    // proves c[j - 1] >= it) — then only the bucket's lowest draw can cross at j - 1.  The one rule for every writer of compact records.
+    bool edge = false;
+    if (edge_code && delta == 1) {
+      const double sp = st.cdf(e - 1) * 16777216.0;
+      const uint32_t cp = sp >= 16777215.0 ? 16777215u : (uint32_t)sp;
+      edge = (uint64_t)cp == (((uint64_t)(uint32_t)j << 24) + (uint32_t)r.deg - 1) / (uint32_t)r.deg;   // ceil(j * 2^24 / deg)
+    }
+    const int32_t d12 = cfo_delta_encode(delta, edge);
     dbits = (uint32_t)d12 & 0xFFFu;
     cg = c | ((dbits & 0xFFu) << 24);
   }
@@ -282,7 +290,7 @@ __device__ inline void cfo_write(const ST &st, const Row *__restrict__ rows /* o
 template <class ST>
 __global__ void k_cfo_rows(const Row *__restrict__ rows, const Row *__restrict__ link_rows, const Ent *__restrict__ ent, ST st,
                            CfoEnt *__restrict__ cfo, int64_t n_slots, int32_t vmin, unsigned long long *escapes,
-                           unsigned long long *next_slot) {
+                           unsigned long long *next_slot, bool edge_code) {
   const int lane = lane_id();
   while (true) {
     unsigned long long grab = 0;
@@ -293,7 +301,7 @@ __global__ void k_cfo_rows(const Row *__restrict__ rows, const Row *__restrict__
     for (int64_t v = (int64_t)grab; v < (int64_t)grab + 4 && v < n_slots; ++v) {
       const Row r = rows[v];
       const bool regular = !(r.flags & ROW_IRREGULAR);
-      for (int32_t j = lane; j < r.deg; j += 64) cfo_write(st, link_rows, ent, vmin, n_slots, r, j, regular, cfo, escapes);
+      for (int32_t j = lane; j < r.deg; j += 64) cfo_write(st, link_rows, ent, vmin, n_slots, r, j, regular, edge_code, cfo, escapes);
     }
   }
 }
@@ -472,8 +480,12 @@ static unsigned long long run_cfo(srw_handle *h, ST st, unsigned long long *esc_
   DevBuf<unsigned long long> next_slot; next_slot.alloc(1);
   SRW_HIP(hipMemsetAsync(next_slot.p, 0, 8, stq));
   SRW_HIP(hipMemsetAsync(esc_word, 0, 8, stq));
+  // A/B and tests: the tables and the pick of before CFO_GD_EDGE — plain deltas, and bucket j's record loaded again when the scan comes
+  // back to it (GraphView::cfo_reload): the same picks, two more dependent loads where the code stands
+  const bool edge_code = !getenv("SRW_NO_EDGE_CODE");
+  g.cfo_plain = !edge_code;
   hipLaunchKernelGGL((k_cfo_rows<ST>), dim3(256 * 8), dim3(256), 0, stq, g.rows.p, link_rows ? link_rows : g.rows.p, g.ent.p, st,
-                     g.cfo.p, g.n_slots, g.vmin, esc_word, next_slot.p);
+                     g.cfo.p, g.n_slots, g.vmin, esc_word, next_slot.p, edge_code);
   unsigned long long n_esc = 0;
   SRW_HIP(hipMemcpyAsync(&n_esc, esc_word, 8, hipMemcpyDeviceToHost, stq));
   SRW_HIP(hipStreamSynchronize(stq));
@@ -489,6 +501,13 @@ void build_first_order_tables(srw_handle *h, bool want_exact) {
   Graph &g = h->g;
   const bool sharded = h->cfg.world > 1;
   if (g.has_cfo_local && !sharded) { g.has_cfo = true; g.has_cfo_local = false; }   // world 1: the local records are the whole graph's
+  // A/B inside ONE allocation (tools/first_order_ab.py --in-place): a handle that holds the exact table too derives its compact records
+  // again, into the buffer they are in, when SRW_NO_EDGE_CODE is not what it was when they were written
+  if (!want_exact && !sharded && g.has_cfo && g.has_fo && g.cfo_plain != (getenv("SRW_NO_EDGE_CODE") != nullptr)) {
+    DevBuf<unsigned long long> esc; esc.alloc(1);
+    if (run_cfo(h, FoStore{g.fo.p}, esc.p) != 0) throw Error(SRW_ERR_INVALID, "compact first-order records: an escape on a table that had none");
+    return;
+  }
   if (want_exact ? g.has_fo : (g.has_cfo || sharded || g.cfo_rejected || g.n_entries == 0) && (g.has_cfo || g.has_fo)) return;
   hipStream_t st = h->stream;
   DevBuf<uint2> items; DevBuf<unsigned long long> n_items;

@@ -130,11 +130,12 @@ __device__ inline CfoEnt load_cfo(const CfoEnt *p) {
 
 // Lattice draw (p = m * 2^-24) through the compact table: same index as fo_pick, one 16-byte load per probe.
 template <bool NT>
-__device__ inline CfoEnt cfo_pick(const CfoEnt *row, int32_t deg, uint32_t m, unsigned &reads, int32_t &k_out) {
+__device__ inline CfoEnt cfo_pick(const CfoEnt *row, int32_t deg, uint32_t m, unsigned &reads, int32_t &k_out, bool reload = false) {
   const uint32_t j = (uint32_t)(((uint64_t)m * (uint64_t)(uint32_t)deg) >> 24);
   CfoEnt e = load_cfo<NT>(row + j);
   reads = 1;
-  const int32_t gd = cfo_delta(e.cg, e.link);
+  // (under CFO_GD_EDGE: 0 for every draw of the bucket but its lowest — the answer is then in e, or behind it)
+  const int32_t gd = cfo_delta(e.cg, e.link, j, m, (uint32_t)deg);
   int32_t k;
   if (gd == CFO_GD_SAT) {                       // delta beyond 12 bits: first k with c_k >= m by bisection (c is monotone)
     int32_t lo = 0, hi = deg;
@@ -149,7 +150,14 @@ __device__ inline CfoEnt cfo_pick(const CfoEnt *row, int32_t deg, uint32_t m, un
     return e;
   }
   k = (int32_t)j - gd;
-  if (gd) { e = load_cfo<NT>(row + k); ++reads; }
+  if (gd > 0) {                                 // the scan starts before j and comes back to it: j's record is kept, not loaded again
+    const CfoEnt ej = e;
+    e = load_cfo<NT>(row + k); ++reads;
+    while ((e.cg & 0xFFFFFFu) < m) {
+      if (++k == (int32_t)j && !reload) { e = ej; break; }        // (reload: GraphView::cfo_reload, the A/B arm)
+      e = load_cfo<NT>(row + k); ++reads;
+    }
+  } else if (gd < 0) { e = load_cfo<NT>(row + k); ++reads; }
   while ((e.cg & 0xFFFFFFu) < m) {              // min(floor(cdf * 2^24), 2^24 - 1) < m  <=>  cdf < p
     ++k;
     if (k >= deg) { k = 0; e = load_cfo<NT>(row); ++reads; break; }   // edges.head fallback (:24)
@@ -159,9 +167,9 @@ __device__ inline CfoEnt cfo_pick(const CfoEnt *row, int32_t deg, uint32_t m, un
   return e;
 }
 template <bool NT>
-__device__ inline CfoEnt cfo_pick(const CfoEnt *row, int32_t deg, uint32_t m, unsigned &reads) {
+__device__ inline CfoEnt cfo_pick(const CfoEnt *row, int32_t deg, uint32_t m, unsigned &reads, bool reload = false) {
   int32_t k;
-  return cfo_pick<NT>(row, deg, m, reads, k);
+  return cfo_pick<NT>(row, deg, m, reads, k, reload);
 }
 
 // Returns the chosen record (id + the neighbor's row descriptor); k_out = its position.

@@ -357,7 +357,7 @@ __global__ __launch_bounds__(TPB) void k_sh_step_cfo(GraphView g, ShardIO io, in
           if (!(link >> 63)) {
             const uint32_t m = walk_bits24(rng.seed, iter, (uint32_t)rng_source(g, wk.src), (uint32_t)step);
             unsigned rd;
-            e = cfo_pick<NT>(g.cfo + off, deg, m, rd); reads += rd;
+            e = cfo_pick<NT>(g.cfo + off, deg, m, rd, g.cfo_reload != 0); reads += rd;
           } else {                                        // irregular row: the reference's scan, literally; the links are valid for every row
             const float u = draw_uniform(rng, iter, (uint32_t)rng_source(g, wk.src), (uint32_t)step);
             e = g.cfo[off + lane_pick_sequential(g.ent + off, deg, nobias, u)]; ++fb;
@@ -734,7 +734,7 @@ __global__ __launch_bounds__(TPB, SRW_SHQ1_WAVES) void k_sh_step_q1(GraphView g,
       const uint32_t iter = (uint32_t)(first_walk + wk.lw % io.batch);
       const uint32_t m = walk_bits24(rng.seed, iter, (uint32_t)rng_source(g, wk.src), (uint32_t)step);
       const CfoEnt *crow = g.cfo + r.off;
-      if (step == 1) { unsigned rd; e = cfo_pick<NT>(crow, r.deg, m, rd, k); reads += rd; }
+      if (step == 1) { unsigned rd; e = cfo_pick<NT>(crow, r.deg, m, rd, k, g.cfo_reload != 0); reads += rd; }
       else {
         uint32_t rv = REV_NONE, pos0 = 0u;
         float w0 = 0.0f;

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(TPB, MINW) void k_walk_first_order(GraphView g, con
         if (COMPACT && !(r.flags & ROW_IRREGULAR)) {          // Philox draw on the 2^-24 lattice: 16-byte records
           const uint32_t m = walk_bits24(rng.seed, iter, (uint32_t)src, (uint32_t)s);
           unsigned rd;
-          const CfoEnt e = cfo_pick<NT>(g.cfo + r.off, r.deg, m, rd); reads += rd;
+          const CfoEnt e = cfo_pick<NT>(g.cfo + r.off, r.deg, m, rd, g.cfo_reload != 0); reads += rd;
           val = e.id; ++len;
           r.off = (int64_t)(e.link & CFO_NOFF_MASK); r.deg = (int32_t)((e.link >> 40) & 0x7FFFFFu);
           r.flags = (e.link >> 63) ? ROW_IRREGULAR : 0u;
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(TPB) void k_walk_q1(GraphView g, const int32_t *__r
         const CfoEnt *crow = g.cfo + r.off;
         CfoEnt e; int32_t k = -1;
         if (s == 1) {                               // initFirstStep: raw weights = the first-order draw
-          unsigned rd; e = cfo_pick<NT>(crow, r.deg, m, rd, k); reads += rd;
+          unsigned rd; e = cfo_pick<NT>(crow, r.deg, m, rd, k, g.cfo_reload != 0); reads += rd;
         } else {
           const int4v rv4 = NT ? __builtin_nontemporal_load(reinterpret_cast<const int4v *>(g.rev + eprev))
                                : *reinterpret_cast<const int4v *>(g.rev + eprev);
@@ -711,6 +711,20 @@ __global__ void k_hook_rng(uint32_t seed, const uint32_t *iter, const uint32_t *
   RngSpec rng; rng.mode = 1; rng.const_r = 0.f; rng.seed = seed;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = draw_uniform(rng, iter[i], src[i], step[i]);
+}
+// cfo_pick on one row, one lattice draw per lane: position and loads issued.  pos = -1: the vertex is not in the graph or has no
+// neighbours, -2: its row is irregular (never sampled through the compact records).
+template <bool NT>
+__global__ void k_hook_cfo_pick(GraphView g, int32_t vertex, const uint32_t *__restrict__ m, int64_t n, int32_t *__restrict__ pos,
+                                int32_t *__restrict__ reads) {
+  const int64_t slot = vertex_slot(vertex, g.rows, g.orig_id, g.n_slots, g.vmin);
+  Row r; r.off = 0; r.deg = 0; r.flags = 0;
+  if (slot < g.n_slots) r = g.rows[slot];
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    int32_t k = r.deg <= 0 ? -1 : -2; unsigned rd = 0;
+    if (r.deg > 0 && !(r.flags & ROW_IRREGULAR)) cfo_pick<NT>(g.cfo + r.off, r.deg, m[i], rd, k, g.cfo_reload != 0);
+    pos[i] = k; reads[i] = (int32_t)rd;
+  }
 }
 
 }  // namespace
@@ -1424,6 +1438,31 @@ void hook_rng(srw_handle *h, uint32_t seed, const uint32_t *iter, const uint32_t
   SRW_HIP(hipGetLastError());
   SRW_HIP(hipMemcpyAsync(out, o.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   SRW_HIP(hipStreamSynchronize(st));
+}
+
+void hook_cfo_pick(srw_handle *h, int32_t vertex, const uint32_t *m, int64_t n, int32_t *pos, int32_t *reads) {
+  if (n <= 0) return;
+  Graph &g = h->g;
+  if (!g.loaded) throw Error(SRW_ERR_INVALID, "no graph loaded");
+  if (h->cfg.world > 1) throw Error(SRW_ERR_INVALID, "srw_cfo_pick: a sharded handle (world > 1) has no whole-graph compact table");
+  for (int64_t i = 0; i < n; ++i)
+    if (m[i] >> 24) throw Error(SRW_ERR_INVALID, "srw_cfo_pick: a draw is not below 2^24");
+  build_first_order_tables(h, false);
+  if (!g.has_cfo) throw Error(SRW_ERR_INVALID, "srw_cfo_pick: this graph has no compact first-order table (a record needs an escape)");
+  hipStream_t st = h->stream;
+  DevBuf<uint32_t> dm; DevBuf<int32_t> dp, dr;
+  dm.alloc((size_t)n); dp.alloc((size_t)n); dr.alloc((size_t)n);
+  SRW_HIP(hipMemcpyAsync(dm.p, m, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  const GraphView gv = g.view();
+  // both load policies of the walk give the same picks; the nontemporal one is the headline kernel's
+  hipLaunchKernelGGL(k_hook_cfo_pick<true>, dim3(blocks), dim3(256), 0, st, gv, vertex, dm.p, n, dp.p, dr.p);
+  SRW_HIP(hipGetLastError());
+  SRW_HIP(hipMemcpyAsync(pos, dp.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  SRW_HIP(hipMemcpyAsync(reads, dr.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  SRW_HIP(hipStreamSynchronize(st));
+  if (pos[0] == -1) throw Error(SRW_ERR_INVALID, "srw_cfo_pick: the vertex is not in the graph or has no neighbours");
+  if (pos[0] == -2) throw Error(SRW_ERR_INVALID, "srw_cfo_pick: the vertex's row is irregular (it is not sampled through the compact records)");
 }
 
 }  // namespace srw
