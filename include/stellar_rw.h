@@ -286,6 +286,56 @@ int32_t srw_vertex_types(const srw_handle *h, int64_t *n);
  * params->flags is ignored. */
 int32_t srw_walk_metapath(srw_handle *h, const srw_walk_params *params, const int32_t *pattern, int32_t m, srw_walk_stats *stats);
 
+/* ---- neighbour sampling: the layered fan-out sample of a mini-batch of seeds (whole-graph handles) ------------
+ * No reference counterpart (the reference only walks); the semantics are those of StellarGraph's SampledBreadthFirstWalk and of the
+ * sampler behind PyG's NeighborLoader / DGL's sample_neighbors, with RandomSample.sample as the weighted draw.  It reads the tables a
+ * p = q = 1 srw_walk builds and nothing else.
+ *
+ * Layout.  F_0 = 1 and F_l = F_{l-1} * fanouts[l-1].  Layer l (1-based, l = 1 .. n_layers) is int32 [n_seeds][F_l], row-major, written to
+ * d_layers[l-1] (the caller's buffers, device memory on the handle's GPU); layer 0 is the seed list d_seeds [n_seeds].  The parent of
+ * element (b, j) of layer l is element (b, j / fanouts[l-1]) of layer l-1.  The tree's edges are implicit in the positions: layer l
+ * viewed as [n_seeds][F_{l-1}][fanouts[l-1]] groups the children by parent — the form GraphSAGE's mean aggregator consumes.  No
+ * relabelling and no edge list are produced; a deduplicated subgraph with a relabelled edge_index is out of scope.
+ *
+ * Ids are the input's ids, also on a graph with compacted ids, as in every other tensor entry point.  An element is -1 when its parent
+ * is -1, when its parent is no present vertex of the graph (below the smallest or above the largest id, in a gap), or when its
+ * parent's row is empty (a dead end, or a destination-only vertex of a directed graph): the whole subtree below a -1 is -1.  -1 is the
+ * padding value and never names a vertex here, not even on a graph that holds a vertex -1.  *n_unknown counts the SEEDS that are no
+ * present vertex, -1 included (deeper layers hold only -1 or ids the graph itself supplied).  No id reaches an address before
+ * device_common.h:vertex_slot has checked it, so no tensor content can send a load or a store outside a table.
+ *
+ * The draw of element (b, j) of layer l:  word = philox4x32_10(ctr = (b, j, l, epoch), key = (seed, 64))[0].  b is the seed's index
+ * WITHIN THE CALL, never the vertex id: a vertex that occurs twice gets independent children, and a seed's subtree does not depend on
+ * what else is in the batch.  Key words 0 .. 32 are taken by the walk and the negatives; 64 is this stream's.
+ *   replace != 0   (StellarGraph's semantics, and the reference's draw)  m = word >> 8, u = m * 2^-24; the element is the entry that
+ *                  RandomSample.sample (M/algorithm/RandomSample.scala:12-25) returns for N(parent) with its raw weights and u — exactly
+ *                  what step 1 of srw_walk does with its own u: S = the f64 left fold of the weights, acc += (double)w / S entry by
+ *                  entry, the first entry with acc >= (double)u, the row's head if there is none.  Multi-edges and self-loops are
+ *                  entries like any other.  The 24-bit lattice has the same consequence as for the walk: of a row beyond 2^24 entries
+ *                  some can never be drawn.
+ *   replace == 0   (PyG's / DGL's default)  uniform over the row's ENTRIES — positions in srw_graph_neighbors order —, ignoring the
+ *                  weights, without repeating a position.  With deg = |N(parent)| and f = fanouts[l-1]: if deg <= f the children are
+ *                  the row's entries in row order, then -1.  Otherwise Floyd's algorithm in selection order, for i = 0 .. f-1:
+ *                  J = deg - f + i, t = (uint64(word_i) * (J + 1)) >> 32 with word_i the word of the child's own output position
+ *                  j = jp * f + i (jp the parent's position in its row of layer l-1); child i is entry t of the row if no earlier
+ *                  child of this parent took position t, else entry J.  Positions are distinct; ids may repeat on a multi-graph.
+ *
+ * The call runs on the handle's stream, one launch per layer (layer l reads layer l-1), and is complete on return; the unknown count
+ * (8 bytes) is the only read-back; every offset is 64-bit (n_seeds * F_l may exceed 2^31).  The first-order tables are built on first
+ * use, exactly as a p = q = 1 srw_walk would build them.  The handle's last walk result, sources, vertex types and negative weights
+ * are untouched.  SRW_NBR_NO_COMPACT in flags is a test switch: draw through the 32-byte first-order records even where the compact
+ * ones exist (the results are the same element for element).
+ * SRW_ERR_INVALID before any launch, the outputs untouched: a NULL h / np / fanouts / d_layers; no graph loaded; a sharded handle
+ * (world > 1); population 1 selected; n_layers outside 1 .. 8; a fanout outside 1 .. 4096; a fanout above 64 with replace == 0;
+ * F_L >= 2^31 (L = n_layers); n_seeds < 0 or >= 2^31; flags with an unknown bit; then, for n_seeds > 0: a NULL d_seeds, a NULL layer
+ * pointer, a pointer that is not 4-byte aligned, a layer's byte range overlapping the seeds' or another layer's.  n_seeds == 0 is
+ * SRW_OK whatever the pointers are (an empty tensor's are arbitrary): nothing is launched, *n_unknown = 0. */
+typedef struct { uint32_t seed; uint32_t epoch; int32_t replace; int32_t flags; } srw_neighbor_params;   /* 16 bytes */
+enum { SRW_NBR_NO_COMPACT = 1 /* test switch: draw through the 32-byte first-order records even where the compact ones exist */ };
+int32_t srw_sample_neighbors(srw_handle *h, const void *d_seeds /* int32 [n_seeds] */, int64_t n_seeds,
+                             const int32_t *fanouts /* host, [n_layers] */, int32_t n_layers, const srw_neighbor_params *np,
+                             void *const *d_layers /* host array of n_layers device pointers */, int64_t *n_unknown /* or NULL */);
+
 /* Pinned (page-locked) host memory for srw_walk_to_host / srw_fetch_paths destinations. */
 int32_t srw_host_alloc(size_t bytes, void **out);
 void srw_host_free(void *p);

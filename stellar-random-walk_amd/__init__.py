@@ -33,6 +33,8 @@ WALK_NO_HUB_BITMAPS = 65536
 WALK_DEVICE_FORMAT = 131072
 WALK_NO_EDGE_TABLES = 262144
 WALK_EDGE_TABLES_ALL = 524288
+NBR_NO_COMPACT = 1               # srw_neighbor_params.flags
+NBR_MAX_LAYERS, NBR_MAX_FANOUT, NBR_MAX_DISTINCT_FANOUT = 8, 4096, 64      # srw_sample_neighbors' limits
 
 
 class W2vParams(C.Structure):
@@ -67,6 +69,10 @@ class TopkParams(C.Structure):
 
 
 TOPK_METRICS = {"cosine": 0, "dot": 1}     # srw_topk_params.metric
+
+
+class NeighborParams(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("epoch", C.c_uint32), ("replace", C.c_int32), ("flags", C.c_int32)]
 
 
 class SrwError(RuntimeError):
@@ -109,7 +115,7 @@ STRATEGIES = ("edge_table", "p1", "p2", "w", "p3", "scan", "prefix", "chain", "e
 EXPORTS = [
     "srw_create", "srw_destroy", "srw_last_error", "srw_set_stream", "srw_plan_walks", "srw_load_edgelist", "srw_load_coo", "srw_load_coo_device",
     "srw_load_adjacency", "srw_generate_rmat", "srw_graph_stats", "srw_graph_vertices", "srw_graph_neighbors",
-    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_vertex_types_set", "srw_vertex_types", "srw_walk_metapath", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
+    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_vertex_types_set", "srw_vertex_types", "srw_walk_metapath", "srw_sample_neighbors", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
     "srw_shard_capacity", "srw_shard_vertex_ranks", "srw_shard_layout_for", "srw_shard_begin", "srw_shard_superstep",
     "srw_shard_flush", "srw_shard_finish", "srw_shard_rows_count", "srw_shard_rows_export", "srw_shard_rows_merge",
     "srw_shard_rows_commit", "srw_shard_rows_release", "srw_device_alloc", "srw_device_free", "srw_cluster_create", "srw_cluster_destroy", "srw_cluster_last_error",
@@ -161,6 +167,7 @@ def lib():
     L.srw_vertex_types_set.argtypes = [vp, vp, C.c_int64]
     L.srw_vertex_types.argtypes = [vp, i64p]
     L.srw_walk_metapath.argtypes = [vp, C.POINTER(WalkParams), i32p, C.c_int32, C.POINTER(WalkStats)]
+    L.srw_sample_neighbors.argtypes = [vp, vp, C.c_int64, i32p, C.c_int32, C.POINTER(NeighborParams), C.POINTER(vp), i64p]
     L.srw_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.srw_host_free.argtypes = [vp]
     L.srw_host_free.restype = None
@@ -646,6 +653,86 @@ class Engine:
         lens = np.empty(max(st.n_walkers, 1), dtype=np.int32)
         self._ck(lib().srw_fetch_paths(self.h, _i32(paths), _i32(lens)))
         return paths[:st.n_walkers], lens[:st.n_walkers], st.as_dict()
+
+    # ---- neighbour sampling: the layered fan-out sample of a mini-batch of seeds (srw_sample_neighbors) ----
+    @staticmethod
+    def _neighbor_fanouts(fanouts, replace):
+        """sample_neighbors' fanouts as int32 [n_layers]; TypeError before the library is called."""
+        if isinstance(fanouts, (str, bytes)) or not hasattr(fanouts, "__len__"):
+            raise TypeError("sample_neighbors: fanouts must be a sequence of integers (got %s)" % type(fanouts).__name__)
+        a = np.asarray(fanouts)
+        if a.ndim != 1 or not 1 <= a.size <= NBR_MAX_LAYERS:
+            raise TypeError("sample_neighbors: fanouts must have 1 .. %d entries (got shape %s)" % (NBR_MAX_LAYERS, a.shape))
+        if a.dtype.kind not in "iu":
+            raise TypeError("sample_neighbors: fanouts must be integers (got %s)" % a.dtype)
+        if int(a.min()) < 1 or int(a.max()) > NBR_MAX_FANOUT:
+            raise TypeError("sample_neighbors: a fanout is outside 1 .. %d" % NBR_MAX_FANOUT)
+        if not replace and int(a.max()) > NBR_MAX_DISTINCT_FANOUT:
+            raise TypeError("sample_neighbors: a fanout above %d needs replace=True" % NBR_MAX_DISTINCT_FANOUT)
+        total = 1
+        for f in a.tolist():
+            total *= int(f)
+        if total >= 2**31:
+            raise TypeError("sample_neighbors: the product of the fanouts must stay below 2^31 (got %d)" % total)
+        return np.array(a, dtype=np.int32)
+
+    def sample_neighbors(self, seeds, fanouts, seed=1, epoch=0, replace=True, return_unknown=False, no_compact=False):
+        """Runs srw_sample_neighbors: the fixed fan-out neighbour sample of a mini-batch (StellarGraph's SampledBreadthFirstWalk, the
+        sampler behind PyG's NeighborLoader / DGL's sample_neighbors).  seeds: a one-dimensional contiguous int32 / int64 torch tensor
+        [B] on the handle's device (int64 is narrowed after a range check), or a host array-like of integers, which is uploaded.
+        Returns a list of len(fanouts) int32 device tensors, layer l of shape [B, F_l] with F_l = fanouts[0] * ... * fanouts[l];
+        with return_unknown the number of seeds that are no vertex of the graph is appended.  Layout rule: the parent of
+        layers[l][b, j] is layers[l-1][b, parent] with parent = j // f_l, f_l = fanouts[l] (the seeds are the parents of layers[0]) —
+        so layers[l].view(B, -1, f_l) groups the children by parent, and a mean aggregation over a feature table X laid out like
+        vertices() is  X[e.rows_of(layer.reshape(-1)).long()].view(B, -1, f_l, D).mean(dim=2)  (rows_of gives -1 for the -1 padding:
+        mask it).  -1 marks a child of -1, of an id that is no vertex, or of a vertex without neighbours.
+        replace=True draws every child by RandomSample.sample over the parent's weighted row (what step 1 of walk does);
+        replace=False takes distinct row positions uniformly, ignoring weights (the whole row, then -1, when it has at most f_l
+        entries; fanouts up to 64).  The draw is keyed by (seed, epoch, the seed's index b, j, layer), never by the vertex id.
+        no_compact: test switch (the 32-byte first-order records).  A wrong dtype, rank, contiguity or device of seeds, fanouts that
+        are no integers or outside the limits: TypeError before the library is called."""
+        fan = self._neighbor_fanouts(fanouts, replace)
+        mine = getattr(self, "device", None)
+        if hasattr(seeds, "data_ptr") and hasattr(seeds, "is_cuda"):
+            t = seeds
+            # (shape, contiguity and dtype first, the device last — skipgram's order: each refusal can be met without a GPU)
+            if t.dim() != 1:
+                raise TypeError("sample_neighbors: seeds must be one-dimensional [B] (got %s)" % (tuple(t.shape),))
+            if not t.is_contiguous():
+                raise TypeError("sample_neighbors: seeds must be contiguous")
+            if str(t.dtype) not in ("torch.int32", "torch.int64"):
+                raise TypeError("sample_neighbors: a tensor of seeds must be torch.int32 or torch.int64 (got %s)" % t.dtype)
+            if not t.is_cuda:
+                raise TypeError("sample_neighbors: a tensor of seeds must be in device memory (got %s)" % t.device)
+            if mine is not None and t.device.index != mine:
+                raise TypeError("sample_neighbors: seeds must be on the handle's device (cuda:%s), got %s" % (mine, t.device))
+            import torch
+            if str(t.dtype) == "torch.int64":
+                if t.numel() and (int(t.min()) < -2**31 or int(t.max()) > 2**31 - 1):
+                    raise ValueError("sample_neighbors: a seed is outside int32")
+                t = t.to(torch.int32)
+        else:
+            a = np.asarray(seeds)
+            if a.ndim != 1:
+                raise TypeError("sample_neighbors: seeds must be one-dimensional [B] (got %s)" % (a.shape,))
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError("sample_neighbors: seeds must be integers (got %s)" % a.dtype)
+            if a.size and (int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1):
+                raise ValueError("sample_neighbors: a seed is outside int32")
+            import torch
+            t = torch.as_tensor(np.array(a, dtype=np.int32)).to(torch.device("cuda", mine or 0))
+        B = int(t.numel())
+        layers, F = [], 1
+        for f in fan.tolist():
+            F *= f
+            layers.append(torch.empty((B, F), dtype=torch.int32, device=t.device))
+        ptrs = (C.c_void_p * len(layers))(*[x.data_ptr() for x in layers])
+        P = NeighborParams(int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, int(bool(replace)), NBR_NO_COMPACT if no_compact else 0)
+        unknown = C.c_int64(0)
+        torch.cuda.current_stream(t.device).synchronize()                # the seeds are written before the handle's stream reads them
+        self._ck(lib().srw_sample_neighbors(self.h, C.c_void_p(t.data_ptr()), B, _i32(fan), int(fan.size), C.byref(P), ptrs,
+                                            C.byref(unknown)))
+        return layers + [unknown.value] if return_unknown else layers
 
     def walk_to_host(self, pinned=True, sources=None, **kw):
         """srw_walk_to_host: all num_walks iterations streamed into host buffers (kernel i overlaps the copy of i-1).

@@ -474,6 +474,44 @@ int32_t srw_walk_metapath(srw_handle *h, const srw_walk_params *params, const in
   });
 }
 
+// ---- neighbour sampling (neighbors.hip) ----
+int32_t srw_sample_neighbors(srw_handle *h, const void *d_seeds, int64_t n_seeds, const int32_t *fanouts, int32_t n_layers,
+                             const srw_neighbor_params *np, void *const *d_layers, int64_t *n_unknown) {
+  if (!h || !np || !fanouts || !d_layers) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_sample_neighbors");
+    if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_sample_neighbors needs a whole-graph handle (world == 1)");
+    need(h->g.loaded, "srw_sample_neighbors: no graph loaded");
+    need(n_layers >= 1 && n_layers <= 8, "srw_sample_neighbors: n_layers must be in 1 .. 8");
+    int64_t F[9];
+    F[0] = 1;
+    for (int32_t l = 1; l <= n_layers; ++l) {
+      const int32_t f = fanouts[l - 1];
+      need(f >= 1 && f <= 4096, "srw_sample_neighbors: a fanout is outside 1 .. 4096");
+      need(np->replace != 0 || f <= 64, "srw_sample_neighbors: a fanout above 64 needs replace != 0 (one child per lane of a wave)");
+      F[l] = F[l - 1] * f;
+      need(F[l] < ((int64_t)1 << 31), "srw_sample_neighbors: the product of the fanouts must stay below 2^31");
+    }
+    need(n_seeds >= 0 && n_seeds < ((int64_t)1 << 31), "srw_sample_neighbors: n_seeds must be in [0, 2^31)");
+    need((np->flags & ~SRW_NBR_NO_COMPACT) == 0, "srw_sample_neighbors: flags holds an unknown bit");
+    if (n_seeds == 0) { if (n_unknown) *n_unknown = 0; return; }     // an empty tensor's pointers are arbitrary; nothing to launch
+    need(d_seeds != nullptr, "srw_sample_neighbors: d_seeds is null");
+    struct { uintptr_t p, bytes; } buf[9];                           // the seeds, then the layers
+    buf[0].p = (uintptr_t)d_seeds; buf[0].bytes = (uintptr_t)n_seeds * 4u;
+    for (int32_t l = 1; l <= n_layers; ++l) {
+      need(d_layers[l - 1] != nullptr, "srw_sample_neighbors: a layer pointer is null");
+      buf[l].p = (uintptr_t)d_layers[l - 1]; buf[l].bytes = (uintptr_t)n_seeds * (uintptr_t)F[l] * 4u;
+    }
+    for (int32_t i = 0; i <= n_layers; ++i) need((buf[i].p & 3u) == 0, "srw_sample_neighbors: a pointer is not aligned to 4 bytes");
+    for (int32_t i = 1; i <= n_layers; ++i)
+      for (int32_t k = 0; k < i; ++k)
+        need(buf[i].p + buf[i].bytes <= buf[k].p || buf[k].p + buf[k].bytes <= buf[i].p,
+             "srw_sample_neighbors: a layer overlaps the seeds or another layer");
+    const int64_t unknown = sample_neighbors(h, (const int32_t *)d_seeds, n_seeds, fanouts, n_layers, *np, (int32_t *const *)d_layers);
+    if (n_unknown) *n_unknown = unknown;
+  });
+}
+
 int32_t srw_host_alloc(size_t bytes, void **out) {
   if (!out) return SRW_ERR_INVALID;
   *out = nullptr;

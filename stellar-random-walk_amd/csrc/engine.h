@@ -202,7 +202,7 @@ struct srw_handle {
   srw::DevBuf<int64_t> sg_off;                   // srw_skipgram_windows: first window of every row [n + 1] ...
   srw::DevBuf<char> sg_temp;                     // ... and rocprim's temporary storage (both kept between calls: one call per training step)
   srw::DevBuf<unsigned long long> vc_slots;      // srw_path_vertex_counts: occurrences per slot [n_slots], then the ids that are no vertex [1]
-  srw::DevBuf<unsigned long long> sgns_skipped;  // srw_sgns_step: windows skipped for an id that is no present vertex [1]; srw_vertex_rows: ids that are no vertex
+  srw::DevBuf<unsigned long long> sgns_skipped;  // srw_sgns_step: windows skipped for an id that is no present vertex [1]; srw_vertex_rows: ids that are no vertex; srw_sample_neighbors: seeds that are no vertex
   srw::DevBuf<char> topk_scratch;                // srw_topk_rows: one pass's candidate lists, staged queries and the skip count (topk.hip)
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
@@ -367,6 +367,12 @@ void vertex_types_set(srw_handle *h, const uint8_t *d_types, int64_t n);
 void vertex_types_clear(srw_handle *h);
 // srw_walk_metapath: every refusal comes before a launch or a change of the handle's walk result
 void run_walk_metapath(srw_handle *h, const srw_walk_params &P, const int32_t *pattern, int32_t m, srw_walk_stats *stats);
+
+// ---- neighbors.hip ----
+// srw_sample_neighbors behind its argument checks (api.cpp), on the handle's stream, one launch per layer, complete on return -> seeds
+// that are no present vertex.  d_layers: host array of n_layers device pointers.  Builds the first-order tables on first use.
+int64_t sample_neighbors(srw_handle *h, const int32_t *d_seeds, int64_t n_seeds, const int32_t *fanouts, int32_t n_layers,
+                         const srw_neighbor_params &np, int32_t *const *d_layers);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);
