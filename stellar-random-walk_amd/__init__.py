@@ -25,6 +25,7 @@ IDS_I32, IDS_I64 = 0, 1          # srw_load_coo_device: element type of the id a
 WALK_FORCE_GENERAL = 1
 WALK_NT_LOADS = 2
 WALK_CACHED_LOADS = 4
+WALK_LEGACY_FLUSH = 8
 WALK_NO_COMPACT = 16
 WALK_NO_PREFIX = 32
 WALK_NO_EDGE_HASH = 64
@@ -553,14 +554,14 @@ class Engine:
     # ---- walk ----
     @staticmethod
     def params(p=1.0, q=1.0, walk_length=80, num_walks=1, first_walk=0, rng="philox", const_r=0.0, seed=42,
-               sampler=SAMPLER_REFERENCE, force_general=False, nt_loads=None, occ=0, compact=True, prefix=True, edge_hash=True, binned=True, binned_tune=0, hub_bitmaps=True, device_format=False, edge_tables=True, edge_tables_all=False):
+               sampler=SAMPLER_REFERENCE, force_general=False, nt_loads=None, occ=0, compact=True, prefix=True, edge_hash=True, binned=True, binned_tune=0, hub_bitmaps=True, device_format=False, edge_tables=True, edge_tables_all=False, legacy_flush=False):
         if sampler == "alias":
             sampler = SAMPLER_ALIAS
         elif sampler == "reference":
             sampler = SAMPLER_REFERENCE
         return WalkParams(np.float32(p), np.float32(q), walk_length, num_walks, first_walk,
                           RNG_CONST if rng == "const" else RNG_PHILOX, np.float32(const_r), seed, sampler,
-                          (WALK_FORCE_GENERAL if force_general else 0) | (0 if nt_loads is None else WALK_NT_LOADS if nt_loads else WALK_CACHED_LOADS) | (occ << 8) | (0 if compact else WALK_NO_COMPACT) | (0 if prefix else WALK_NO_PREFIX) | (0 if edge_hash else WALK_NO_EDGE_HASH) | (0 if binned else WALK_NO_BINNED) | (0 if hub_bitmaps else WALK_NO_HUB_BITMAPS) | (WALK_DEVICE_FORMAT if device_format else 0) | (binned_tune << 12) | (0 if edge_tables else WALK_NO_EDGE_TABLES) | (WALK_EDGE_TABLES_ALL if edge_tables_all else 0))
+                          (WALK_FORCE_GENERAL if force_general else 0) | (0 if nt_loads is None else WALK_NT_LOADS if nt_loads else WALK_CACHED_LOADS) | (occ << 8) | (0 if compact else WALK_NO_COMPACT) | (0 if prefix else WALK_NO_PREFIX) | (0 if edge_hash else WALK_NO_EDGE_HASH) | (0 if binned else WALK_NO_BINNED) | (0 if hub_bitmaps else WALK_NO_HUB_BITMAPS) | (WALK_DEVICE_FORMAT if device_format else 0) | (binned_tune << 12) | (0 if edge_tables else WALK_NO_EDGE_TABLES) | (WALK_EDGE_TABLES_ALL if edge_tables_all else 0) | (WALK_LEGACY_FLUSH if legacy_flush else 0))
 
     def walk(self, fetch=True, sources=None, **kw):
         """Runs srw_walk.  Returns (paths [nWalkers, L+2] int32 (-1 tail), lens, stats dict) or just stats.

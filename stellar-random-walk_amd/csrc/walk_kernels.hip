@@ -28,7 +28,12 @@ namespace {
 constexpr int TILE = 16;  // path slots staged in LDS between flushes (64 B per walker per flush)
 
 // ---------------------------------------------------------------------------------------------------------
-template <bool NT, int MINW, bool COMPACT>
+// How the LDS image (a ring of TILE slots per walker) goes out: a row is stored when the slot just written ends a 64-byte line of ITS
+// addresses, so every run lies inside one aligned line (tests/path_flush_ref.py restates the rule).  LEGACY
+// (SRW_WALK_LEGACY_FLUSH, the A/B arm of tools/first_order_ab.py --arm flush): every TILE steps, slots [s - 15, s] of every row — the runs
+// start wherever the row does.  (128-byte lines over a ring of 32 slots, 32 KB per block: measured, 1.3 % against 1.7 % at RMAT-26,
+// profiles/r08_path_flush.md.)
+template <bool NT, int MINW, bool COMPACT, bool LEGACY>
 __global__ __launch_bounds__(TPB, MINW) void k_walk_first_order(GraphView g, const int32_t *__restrict__ verts,
                                                           int64_t n_verts, int64_t n_walkers, int32_t L,
                                                           int32_t first_walk, RngSpec rng,
@@ -54,6 +59,10 @@ __global__ __launch_bounds__(TPB, MINW) void k_walk_first_order(GraphView g, con
   Bias nobias; nobias.second_order = false; nobias.need_member = false; nobias.p = nobias.q = 1.0f;
   nobias.prev = 0; nobias.prev_sids = nullptr; nobias.prev_deg = 0; nobias.vmin = g.vmin;
   tile[wv][lane][0] = src;
+  // position of the row's slot 0 inside its 64-byte line, from the ADDRESS: any base pointer and any stride are right
+  const uint32_t pbase = (uint32_t)(reinterpret_cast<uintptr_t>(paths) >> 2);
+  const uint32_t a_own = (pbase + (uint32_t)wi * (uint32_t)stride) & (TILE - 1);
+  if (!LEGACY && wi < n_walkers && a_own == TILE - 1) paths[wi * stride] = src;     // slot 0 ends a line: due at s = 0, a window of one slot
   src = rng_source(g, src);                            // from here on src only keys the Philox stream (compacted ids: the input's id)
   for (int32_t s = 1; s <= L + 1; ++s) {
     const int c = s & (TILE - 1);
@@ -92,17 +101,45 @@ __global__ __launch_bounds__(TPB, MINW) void k_walk_first_order(GraphView g, con
       }
     }
     tile[wv][lane][c] = val;
-    if (c == TILE - 1 || s == L + 1) {
-      const int ncols = c + 1;
-      const int64_t base_slot = s - c;
-      __syncthreads();   // (the tile is private to the wave; a wave-level barrier measured the same, 64.1 vs 64.4 ms)
+    if constexpr (LEGACY) {
+      if (c == TILE - 1 || s == L + 1) {
+        const int ncols = c + 1;
+        const int64_t base_slot = s - c;
+        __syncthreads();   // (the tile is private to the wave; a wave-level barrier measured the same, 64.1 vs 64.4 ms)
 #pragma unroll
-      for (int rr = 0; rr < 16; ++rr) {
-        int row = rr * 4 + (lane >> 4), col = lane & 15;
-        int64_t w = wave_base + row;
-        if (col < ncols && w < n_walkers) paths[w * stride + base_slot + col] = tile[wv][row][col];
+        for (int rr = 0; rr < 16; ++rr) {
+          int row = rr * 4 + (lane >> 4), col = lane & 15;
+          int64_t w = wave_base + row;
+          if (col < ncols && w < n_walkers) paths[w * stride + base_slot + col] = tile[wv][row][col];
+        }
+        __syncthreads();
       }
-      __syncthreads();
+    } else {
+      // due: slot s ends a line of this row, or the row.  A slot's ring entry is written again TILE steps later, after the row was due.
+      const bool due = wi < n_walkers && ((((a_own + (uint32_t)s) & (TILE - 1)) == TILE - 1) || s == L + 1);
+      unsigned long long todo = __ballot(due);
+      if (todo) {                                        // (wave-uniform; the tile is private to the wave: LDS serves it in order)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int grp = lane / TILE, col = lane & (TILE - 1);
+        do {                                             // 64 / TILE due rows per store instruction, TILE lanes each
+          int row = -1;
+#pragma unroll
+          for (int k = 0; k < 64 / TILE; ++k) {
+            const int b = todo ? (int)__builtin_ctzll(todo) : -1;
+            todo &= todo - 1;                            // (0 stays 0)
+            if (grp == k) row = b;
+          }
+          if (row >= 0) {
+            const int64_t w = wave_base + row;           // < n_walkers: the row was due
+            const uint32_t a = (pbase + (uint32_t)w * (uint32_t)stride) & (TILE - 1);
+            const int32_t t = s - (int32_t)((a + (uint32_t)s) & (TILE - 1)) + col;      // the line's first slot + col
+            if (t >= 0 && t <= s) paths[w * stride + t] = tile[wv][row][t & (TILE - 1)];
+          }
+        } while (todo);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
     }
   }
   if (wi < n_walkers) lens[wi] = len;
@@ -855,9 +892,12 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
     // 16-byte compact records: Philox draws only (p = m * 2^-24), and only if the whole graph qualified at build time
     const bool compact = g.has_cfo && P.rng_mode == SRW_RNG_PHILOX && !(P.flags & SRW_WALK_NO_COMPACT);
     first_order_compact = compact;
-#define SRW_LAUNCH_FO(NTV, MW, CP)                                                                                  \
-  hipLaunchKernelGGL((k_walk_first_order<NTV, MW, CP>), dim3((unsigned)blocks), dim3(TPB), 0, st, gv, verts,           \
+    const bool legacy_flush = (P.flags & SRW_WALK_LEGACY_FLUSH) != 0;
+#define SRW_LAUNCH_FO_W(NTV, MW, CP, LG)                                                                            \
+  hipLaunchKernelGGL((k_walk_first_order<NTV, MW, CP, LG>), dim3((unsigned)blocks), dim3(TPB), 0, st, gv, verts,       \
                      n_verts, n_walkers, P.walk_length, first_walk, rng, d_paths, d_lens, h->counters.p)
+#define SRW_LAUNCH_FO(NTV, MW, CP)                                                                                  \
+  do { if (legacy_flush) SRW_LAUNCH_FO_W(NTV, MW, CP, true); else SRW_LAUNCH_FO_W(NTV, MW, CP, false); } while (0)
     if (compact) {
       const bool ntc = (P.flags & SRW_WALK_NT_LOADS) ? true : (P.flags & SRW_WALK_CACHED_LOADS) ? false
                        : (size_t)g.n_entries * sizeof(CfoEnt) > ((size_t)2 << 30);
@@ -865,6 +905,7 @@ LaunchInfo launch_walk(srw_handle *h, const srw_walk_params &P, int32_t num_walk
     } else if (nt) { if (occ == 8) SRW_LAUNCH_FO(true, 8, false); else if (occ == 7) SRW_LAUNCH_FO(true, 7, false); else SRW_LAUNCH_FO(true, 1, false); }
     else    { if (occ == 8) SRW_LAUNCH_FO(false, 8, false); else if (occ == 7) SRW_LAUNCH_FO(false, 7, false); else SRW_LAUNCH_FO(false, 1, false); }
 #undef SRW_LAUNCH_FO
+#undef SRW_LAUNCH_FO_W
   } else {
     // persistent waves taking walkers from a cursor: enough blocks to fill every CU at the kernel's occupancy
     int64_t blocks = std::min<int64_t>((n_walkers * 64 + TPB - 1) / TPB, (int64_t)h->n_cus * 8);

@@ -12,7 +12,13 @@ against plain built first, second against second) — a difference that follows 
 --in-place takes the allocation out altogether: one engine that also holds the 32-byte table derives its compact records again, into
 the buffer they are in, whenever the switch changes — the arms then differ in the table's CONTENTS only.
 
-usage: first_order_ab.py [--scale 26] [--launches 10] [--warmups 2] [--rounds 1] [--plain-first 0] [--in-place]
+--arm flush compares the two forms of the path flush instead (include/stellar_rw.h: SRW_WALK_LEGACY_FLUSH, the keyword legacy_flush):
+one engine, one table, one path buffer; the flag alternates per block of launches (aligned legacy legacy aligned ...), --rounds blocks
+per arm, and every block's paths and lens are compared on the device with the first block's.  It counts as a gain when the paths are
+identical, every block median of the aligned arm is below every block median of the legacy arm, and the median gain is larger than the
+larger arm's spread (the rule of profiles/r07_edge_code.md).
+
+usage: first_order_ab.py [--arm edge|flush] [--scale 26] [--launches 10] [--warmups 2] [--rounds 1] [--plain-first 0] [--in-place]
 """
 import json
 import os
@@ -116,10 +122,73 @@ def in_place(pkg, torch, scale, ef, L, K, W, blocks):
         eng.close()
 
 
+def one_engine(pkg, torch, scale, ef, L, K, W, blocks, names, arm_of, compare=True):
+    """ONE engine and ONE table; arm_of(name) -> (walk keywords, environment) of an arm.  `blocks` blocks of W warm-ups and K timed
+    launches per arm in the order A B B A ..., every block walking the same iterations.  -> {arm: {...}}, paths identical."""
+    eng = pkg.Engine(device=0)
+    try:
+        eng.generate_rmat(scale, ef << scale, seed=42)
+        arms = {name: {"ms": [], "blocks": []} for name in names}
+        ref_paths, same = None, True
+        for b in range(2 * blocks):
+            name = names[(b + b // 2) % 2]
+            kw, env = arm_of(name)
+            os.environ.update(env)
+            try:
+                ms = []
+                for it in range(W + K):
+                    st = eng.walk(fetch=False, walk_length=L, num_walks=1, first_walk=it, seed=42, **kw)
+                    assert st["kernel_kind"] == 1 and st["record_bytes"] == 16, st
+                    if it >= W:
+                        ms.append(st["kernel_ms"])
+            finally:
+                for k in env:
+                    os.environ.pop(k, None)
+            if compare:
+                pa, la = eng.paths_tensor()
+                if ref_paths is None:
+                    ref_paths = (pa.clone(), la.clone())
+                else:
+                    same = same and same_on_device(torch, pa, ref_paths[0]) and bool(torch.equal(la, ref_paths[1]))
+            arms[name]["ms"] += ms; arms[name]["blocks"].append(statistics.median(ms)); arms[name]["last"] = st
+            print("  block %d %s: %s ms" % (b, name, " ".join("%.3f" % x for x in ms)), flush=True)
+        out = {}
+        for name in names:
+            a, st = arms[name], arms[name]["last"]
+            out[name] = {"kernel_ms": [round(x, 4) for x in a["ms"]], "block_medians_ms": a["blocks"], "median_ms": statistics.median(a["ms"]),
+                         "spread_ms": max(a["ms"]) - min(a["ms"]), "n_steps": st["n_steps"], "ent_reads": st["ent_reads"],
+                         "records_per_step": st["ent_reads"] / max(st["n_steps"], 1)}
+        return out, same
+    finally:
+        eng.close()
+
+
+def summary(out, rounds, new, old, same):
+    """The one-engine arms' figures and the rule: all of new's block medians below all of old's, the gain above the larger spread."""
+    for name in (new, old):
+        ms = rounds[0][name]["kernel_ms"]
+        out[name] = {"median_ms": statistics.median(ms), "spread_ms": max(ms) - min(ms), "min_ms": min(ms), "max_ms": max(ms),
+                     "block_medians_ms": rounds[0][name]["block_medians_ms"], "records_per_step": rounds[0][name]["records_per_step"]}
+        print("%s: median %.3f ms over %d launches, spread %.3f ms (min %.3f, max %.3f), block medians %s" %
+              (name, out[name]["median_ms"], len(ms), out[name]["spread_ms"], min(ms), max(ms),
+               " ".join("%.3f" % x for x in out[name]["block_medians_ms"])))
+    gain = out[old]["median_ms"] - out[new]["median_ms"]
+    out["gain_ms"] = gain
+    out["gain_frac"] = gain / out[old]["median_ms"]
+    out["larger_spread_ms"] = max(out[new]["spread_ms"], out[old]["spread_ms"])
+    out["gain_exceeds_spread"] = bool(gain > out["larger_spread_ms"])
+    out["blocks_separated"] = bool(max(out[new]["block_medians_ms"]) < min(out[old]["block_medians_ms"]))
+    out["is_gain"] = bool(same and out["gain_exceeds_spread"] and out["blocks_separated"])
+    print("paths identical: %s; %s is %.3f ms (%.2f %%) below %s; larger spread %.3f ms; block medians separated: %s; a gain by the rule: %s" %
+          (same, new, gain, 100.0 * out["gain_frac"], old, out["larger_spread_ms"], out["blocks_separated"], out["is_gain"]))
+    return out
+
+
 def main():
     import argparse
     import torch
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--arm", choices=("edge", "flush"), default="edge", help="edge: CFO_GD_EDGE against plain deltas; flush: the aligned path flush against SRW_WALK_LEGACY_FLUSH")
     ap.add_argument("--scale", type=int, default=26)
     ap.add_argument("--edge-factor", type=int, default=16)
     ap.add_argument("--walk-length", type=int, default=80)
@@ -136,6 +205,14 @@ def main():
     pkg = _pkg.load()
     torch.zeros(1, device="cuda")
     rounds, same = [], True
+    if args.arm == "flush":
+        res, same = one_engine(pkg, torch, scale, ef, L, K, W, R, ("aligned", "legacy"), lambda name: ({"legacy_flush": name == "legacy"}, {}))
+        out = {"arm": "flush", "scale": scale, "edge_factor": ef, "walk_length": L, "launches": K, "warmups": W, "blocks_per_arm": R,
+               "paths_identical": bool(same)}
+        print(json.dumps(summary(out, [res], "aligned", "legacy", same)), flush=True)
+        if not same:
+            raise SystemExit("the two arms' paths differ")
+        return
     if args.in_place:
         res, same = in_place(pkg, torch, scale, ef, L, K, W, R)
         res["built_first"] = "one engine, in place"
