@@ -337,6 +337,47 @@ int32_t srw_sample_neighbors(srw_handle *h, const void *d_seeds /* int32 [n_seed
                              const int32_t *fanouts /* host, [n_layers] */, int32_t n_layers, const srw_neighbor_params *np,
                              void *const *d_layers /* host array of n_layers device pointers */, int64_t *n_unknown /* or NULL */);
 
+/* Importance neighbours (importance.hip): PinSAGE's neighbourhood of a seed — the T vertices that R short random walks with
+ * restart from it visit most often, with the visit counts as importance weights (DGL's PinSAGESampler / RandomWalkNeighborSampler; with a
+ * long horizon the Monte-Carlo estimate of personalised PageRank).  No reference counterpart.  R = num_walks, L = walk_length, T = top.
+ *
+ * The walks.  Seed b is the seed's index WITHIN THE CALL, never the vertex id.  It runs walks w = 0 .. R-1, each of at most L steps
+ * s = 0 .. L-1, and step s of walk w has  words = philox4x32_10(ctr = (base + b, w, s, epoch), key = (seed, 65)).  Key word 65 is this
+ * stream's (0 .. 32 and 64 are taken).  base lets a long list be processed in several calls with the same result as one call: seed b of
+ * a call with base = k gets exactly what seed k + b of a call with base = 0 gets.  The walk stands on curr, the seed at s = 0.  Before a
+ * step s >= 1 the walk ends if (words[1] >> 8) < restart_m (restart_m in 0 .. 2^24: 0 means never, 2^24 means always — every walk is then
+ * exactly one step; the first step is never cut).  The walk also ends if N(curr) is empty.  Otherwise m = words[0] >> 8, u = m * 2^-24,
+ * and next is the entry that RandomSample.sample (M/algorithm/RandomSample.scala:12-25) returns for N(curr) with its raw weights and u —
+ * step 1 of srw_walk, and srw_sample_neighbors with replace != 0, with another u, the 24-bit lattice included.  The walk is first-order
+ * at every step: no p, no q, no previous vertex.  Arriving at next is one visit; then curr = next.
+ *
+ * The counts.  c(v) is the number of visits of v over the R walks of this seed.  Without SRW_IMP_KEEP_SEED the visits of the seed's own
+ * vertex are dropped (the walk still passes through it).  d_total[b] is the sum of c(v) over all v, after that drop and before any
+ * truncation: at most R * L.  The result row of b is the vertices with c(v) > 0 ordered by c descending, then by id ascending (the
+ * input's id, as a signed int32); the first T of them go to d_ids[b] with their c in d_counts[b]; padding is id -1 with count 0.  Ids are
+ * the input's ids, also on a graph with compacted ids.  A seed that is -1 or no present vertex gets an all-padding row and total 0 and is
+ * counted in *n_unknown; a present seed with an empty row gets the same row and total 0 but is not counted.  A vertex that occurs twice
+ * in the batch gets independent walks, and a seed's row does not depend on what else is in the batch.  Only the seed is an id a tensor
+ * supplies: it reaches no address before device_common.h:vertex_slot has checked it; every later vertex is one the graph itself supplied.
+ *
+ * The call runs on the handle's stream and is complete on return; the unknown count (8 bytes) is the only read-back; every offset is
+ * 64-bit.  The visits of a chunk of seeds are kept in a buffer of the handle of at most 1 GiB; more seeds than fit are processed chunk
+ * after chunk on the stream.  The first-order tables are built on first use, exactly as a p = q = 1 srw_walk would build them.  The
+ * handle's last walk result, sources, vertex types and negative weights are untouched.  SRW_IMP_NO_COMPACT is a test switch, as
+ * SRW_NBR_NO_COMPACT (the results are the same element for element).
+ * SRW_ERR_INVALID before any launch, the outputs untouched: a NULL h / ip; no graph loaded; a sharded handle (world > 1); population 1
+ * selected; num_walks outside 1 .. 4096; walk_length outside 1 .. 4096; num_walks * walk_length > 4096; top outside 1 .. 64;
+ * restart_m > 2^24; flags with an unknown bit; n_seeds < 0 or >= 2^31; base + n_seeds > 2^32; then, for n_seeds > 0: a NULL d_seeds /
+ * d_ids / d_counts, a pointer that is not 4-byte aligned, any two of the four byte ranges (three when d_total is NULL) overlapping.
+ * n_seeds == 0 is SRW_OK whatever the pointers are: nothing is launched, *n_unknown = 0. */
+typedef struct { uint32_t seed; uint32_t epoch; uint32_t base; int32_t num_walks; int32_t walk_length;
+                 int32_t top; uint32_t restart_m; int32_t flags; } srw_importance_params;   /* 32 bytes */
+enum { SRW_IMP_KEEP_SEED = 1, SRW_IMP_NO_COMPACT = 2 /* test switch, as SRW_NBR_NO_COMPACT */ };
+int32_t srw_importance_neighbors(srw_handle *h, const void *d_seeds /* int32 [n_seeds] */, int64_t n_seeds,
+                                 const srw_importance_params *ip, void *d_ids /* int32 [n_seeds][top] */,
+                                 void *d_counts /* int32 [n_seeds][top] */, void *d_total /* int32 [n_seeds], or NULL */,
+                                 int64_t *n_unknown /* or NULL */);
+
 /* Pinned (page-locked) host memory for srw_walk_to_host / srw_fetch_paths destinations. */
 int32_t srw_host_alloc(size_t bytes, void **out);
 void srw_host_free(void *p);

@@ -36,6 +36,8 @@ WALK_NO_EDGE_TABLES = 262144
 WALK_EDGE_TABLES_ALL = 524288
 NBR_NO_COMPACT = 1               # srw_neighbor_params.flags
 NBR_MAX_LAYERS, NBR_MAX_FANOUT, NBR_MAX_DISTINCT_FANOUT = 8, 4096, 64      # srw_sample_neighbors' limits
+IMP_KEEP_SEED, IMP_NO_COMPACT = 1, 2                                       # srw_importance_params.flags
+IMP_MAX_WALKS, IMP_MAX_LENGTH, IMP_MAX_VISITS, IMP_MAX_TOP = 4096, 4096, 4096, 64   # srw_importance_neighbors' limits
 
 
 class W2vParams(C.Structure):
@@ -74,6 +76,11 @@ TOPK_METRICS = {"cosine": 0, "dot": 1}     # srw_topk_params.metric
 
 class NeighborParams(C.Structure):
     _fields_ = [("seed", C.c_uint32), ("epoch", C.c_uint32), ("replace", C.c_int32), ("flags", C.c_int32)]
+
+
+class ImportanceParams(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("epoch", C.c_uint32), ("base", C.c_uint32), ("num_walks", C.c_int32),
+                ("walk_length", C.c_int32), ("top", C.c_int32), ("restart_m", C.c_uint32), ("flags", C.c_int32)]
 
 
 class SrwError(RuntimeError):
@@ -116,7 +123,7 @@ STRATEGIES = ("edge_table", "p1", "p2", "w", "p3", "scan", "prefix", "chain", "e
 EXPORTS = [
     "srw_create", "srw_destroy", "srw_last_error", "srw_set_stream", "srw_plan_walks", "srw_load_edgelist", "srw_load_coo", "srw_load_coo_device",
     "srw_load_adjacency", "srw_generate_rmat", "srw_graph_stats", "srw_graph_vertices", "srw_graph_neighbors",
-    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_vertex_types_set", "srw_vertex_types", "srw_walk_metapath", "srw_sample_neighbors", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
+    "srw_graph_partition", "srw_alias_row", "srw_walk", "srw_walk_to_host", "srw_walk_and_save", "srw_set_sources", "srw_set_sources_device", "srw_clear_sources", "srw_sources", "srw_vertex_types_set", "srw_vertex_types", "srw_walk_metapath", "srw_sample_neighbors", "srw_importance_neighbors", "srw_host_alloc", "srw_host_free", "srw_fetch_paths", "srw_device_paths", "srw_write_paths",
     "srw_shard_capacity", "srw_shard_vertex_ranks", "srw_shard_layout_for", "srw_shard_begin", "srw_shard_superstep",
     "srw_shard_flush", "srw_shard_finish", "srw_shard_rows_count", "srw_shard_rows_export", "srw_shard_rows_merge",
     "srw_shard_rows_commit", "srw_shard_rows_release", "srw_device_alloc", "srw_device_free", "srw_cluster_create", "srw_cluster_destroy", "srw_cluster_last_error",
@@ -169,6 +176,7 @@ def lib():
     L.srw_vertex_types.argtypes = [vp, i64p]
     L.srw_walk_metapath.argtypes = [vp, C.POINTER(WalkParams), i32p, C.c_int32, C.POINTER(WalkStats)]
     L.srw_sample_neighbors.argtypes = [vp, vp, C.c_int64, i32p, C.c_int32, C.POINTER(NeighborParams), C.POINTER(vp), i64p]
+    L.srw_importance_neighbors.argtypes = [vp, vp, C.c_int64, C.POINTER(ImportanceParams), vp, vp, vp, i64p]
     L.srw_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.srw_host_free.argtypes = [vp]
     L.srw_host_free.restype = None
@@ -677,6 +685,40 @@ class Engine:
             raise TypeError("sample_neighbors: the product of the fanouts must stay below 2^31 (got %d)" % total)
         return np.array(a, dtype=np.int32)
 
+    def _seed_tensor(self, seeds, what):
+        """the seeds of sample_neighbors / importance_neighbors as a contiguous int32 tensor [B] on the handle's device; TypeError for a
+        wrong dtype, rank, contiguity or device before the library is called"""
+        mine = getattr(self, "device", None)
+        if hasattr(seeds, "data_ptr") and hasattr(seeds, "is_cuda"):
+            t = seeds
+            # (shape, contiguity and dtype first, the device last — skipgram's order: each refusal can be met without a GPU)
+            if t.dim() != 1:
+                raise TypeError("%s: seeds must be one-dimensional [B] (got %s)" % (what, tuple(t.shape)))
+            if not t.is_contiguous():
+                raise TypeError("%s: seeds must be contiguous" % what)
+            if str(t.dtype) not in ("torch.int32", "torch.int64"):
+                raise TypeError("%s: a tensor of seeds must be torch.int32 or torch.int64 (got %s)" % (what, t.dtype))
+            if not t.is_cuda:
+                raise TypeError("%s: a tensor of seeds must be in device memory (got %s)" % (what, t.device))
+            if mine is not None and t.device.index != mine:
+                raise TypeError("%s: seeds must be on the handle's device (cuda:%s), got %s" % (what, mine, t.device))
+            import torch
+            if str(t.dtype) == "torch.int64":
+                if t.numel() and (int(t.min()) < -2**31 or int(t.max()) > 2**31 - 1):
+                    raise ValueError("%s: a seed is outside int32" % what)
+                t = t.to(torch.int32)
+        else:
+            a = np.asarray(seeds)
+            if a.ndim != 1:
+                raise TypeError("%s: seeds must be one-dimensional [B] (got %s)" % (what, a.shape))
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError("%s: seeds must be integers (got %s)" % (what, a.dtype))
+            if a.size and (int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1):
+                raise ValueError("%s: a seed is outside int32" % what)
+            import torch
+            t = torch.as_tensor(np.array(a, dtype=np.int32)).to(torch.device("cuda", mine or 0))
+        return t
+
     def sample_neighbors(self, seeds, fanouts, seed=1, epoch=0, replace=True, return_unknown=False, no_compact=False):
         """Runs srw_sample_neighbors: the fixed fan-out neighbour sample of a mini-batch (StellarGraph's SampledBreadthFirstWalk, the
         sampler behind PyG's NeighborLoader / DGL's sample_neighbors).  seeds: a one-dimensional contiguous int32 / int64 torch tensor
@@ -693,35 +735,8 @@ class Engine:
         no_compact: test switch (the 32-byte first-order records).  A wrong dtype, rank, contiguity or device of seeds, fanouts that
         are no integers or outside the limits: TypeError before the library is called."""
         fan = self._neighbor_fanouts(fanouts, replace)
-        mine = getattr(self, "device", None)
-        if hasattr(seeds, "data_ptr") and hasattr(seeds, "is_cuda"):
-            t = seeds
-            # (shape, contiguity and dtype first, the device last — skipgram's order: each refusal can be met without a GPU)
-            if t.dim() != 1:
-                raise TypeError("sample_neighbors: seeds must be one-dimensional [B] (got %s)" % (tuple(t.shape),))
-            if not t.is_contiguous():
-                raise TypeError("sample_neighbors: seeds must be contiguous")
-            if str(t.dtype) not in ("torch.int32", "torch.int64"):
-                raise TypeError("sample_neighbors: a tensor of seeds must be torch.int32 or torch.int64 (got %s)" % t.dtype)
-            if not t.is_cuda:
-                raise TypeError("sample_neighbors: a tensor of seeds must be in device memory (got %s)" % t.device)
-            if mine is not None and t.device.index != mine:
-                raise TypeError("sample_neighbors: seeds must be on the handle's device (cuda:%s), got %s" % (mine, t.device))
-            import torch
-            if str(t.dtype) == "torch.int64":
-                if t.numel() and (int(t.min()) < -2**31 or int(t.max()) > 2**31 - 1):
-                    raise ValueError("sample_neighbors: a seed is outside int32")
-                t = t.to(torch.int32)
-        else:
-            a = np.asarray(seeds)
-            if a.ndim != 1:
-                raise TypeError("sample_neighbors: seeds must be one-dimensional [B] (got %s)" % (a.shape,))
-            if a.size and a.dtype.kind not in "iu":
-                raise TypeError("sample_neighbors: seeds must be integers (got %s)" % a.dtype)
-            if a.size and (int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1):
-                raise ValueError("sample_neighbors: a seed is outside int32")
-            import torch
-            t = torch.as_tensor(np.array(a, dtype=np.int32)).to(torch.device("cuda", mine or 0))
+        t = self._seed_tensor(seeds, "sample_neighbors")
+        import torch
         B = int(t.numel())
         layers, F = [], 1
         for f in fan.tolist():
@@ -734,6 +749,73 @@ class Engine:
         self._ck(lib().srw_sample_neighbors(self.h, C.c_void_p(t.data_ptr()), B, _i32(fan), int(fan.size), C.byref(P), ptrs,
                                             C.byref(unknown)))
         return layers + [unknown.value] if return_unknown else layers
+
+    # ---- importance neighbours: walks with restart, the top-T vertices by visit count (srw_importance_neighbors) ----
+    @staticmethod
+    def _importance_shape(num_walks, walk_length, top):
+        """importance_neighbors' (R, L, T) as ints; TypeError before the library is called."""
+        out = []
+        for name, v, hi in (("num_walks", num_walks, IMP_MAX_WALKS), ("walk_length", walk_length, IMP_MAX_LENGTH), ("top", top, IMP_MAX_TOP)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError("importance_neighbors: %s must be an integer (got %s)" % (name, type(v).__name__))
+            if not 1 <= int(v) <= hi:
+                raise TypeError("importance_neighbors: %s is outside 1 .. %d (got %d)" % (name, hi, int(v)))
+            out.append(int(v))
+        if out[0] * out[1] > IMP_MAX_VISITS:
+            raise TypeError("importance_neighbors: num_walks * walk_length must not exceed %d (got %d)" % (IMP_MAX_VISITS, out[0] * out[1]))
+        return tuple(out)
+
+    @staticmethod
+    def _importance_restart(restart, restart_m=None):
+        """restart in [0, 1] -> restart_m = round(restart * 2^24) in 0 .. 2^24 (an integer restart_m overrides it); TypeError otherwise."""
+        if restart_m is not None:
+            if isinstance(restart_m, (bool, np.bool_)) or not isinstance(restart_m, (int, np.integer)) or not 0 <= int(restart_m) <= 2**24:
+                raise TypeError("importance_neighbors: restart_m must be an integer in 0 .. 2^24 (got %r)" % (restart_m,))
+            return int(restart_m)
+        if isinstance(restart, (bool, np.bool_)) or not isinstance(restart, (int, float, np.integer, np.floating)):
+            raise TypeError("importance_neighbors: restart must be a number in [0, 1] (got %s)" % type(restart).__name__)
+        if not 0.0 <= float(restart) <= 1.0:                             # (NaN fails both compares)
+            raise TypeError("importance_neighbors: restart must be in [0, 1] (got %r)" % (restart,))
+        return int(round(float(restart) * 2**24))
+
+    def importance_neighbors(self, seeds, num_walks, walk_length, top, restart=0.5, seed=1, epoch=0, base=0, keep_seed=False,
+                             return_total=False, return_unknown=False, no_compact=False, restart_m=None):
+        """Runs srw_importance_neighbors: PinSAGE's importance neighbourhood (DGL's PinSAGESampler / RandomWalkNeighborSampler).  Every
+        seed runs num_walks first-order random walks of at most walk_length steps; before every step but the first a walk ends with
+        probability restart; the top vertices by visit count, ties by id ascending, are the seed's neighbours.  seeds: as in
+        sample_neighbors — a one-dimensional contiguous int32 / int64 torch tensor [B] on the handle's device (int64 is narrowed after
+        a range check), or a host array-like of integers, which is uploaded.  Returns (ids, counts), int32 device tensors [B, top]
+        (padding: id -1, count 0), followed by total [B] (all visits of the seed, before the cut to top) with return_total and by the
+        number of seeds that are no vertex with return_unknown.  Visits of the seed itself are dropped unless keep_seed.  The draw is
+        keyed by (seed, epoch, base + the seed's index b, walk, step), never by the vertex id: a list split over several calls with
+        base = the offset of each part gives what one call gives.
+        PinSAGE use: the neighbours of a batch and their edge weights are
+            ids, counts, total = e.importance_neighbors(batch, 200, 2, 50, return_total=True)
+            weights = counts.float() / total.clamp(min=1)[:, None]          # importance pooling; mask ids == -1
+        and X[e.rows_of(ids.reshape(-1)).long()] gathers their features.  PPR reading: with keep_seed, counts / (num_walks summed over
+        epochs) estimates sum_{k=1..walk_length} (1 - restart)^(k-1) (P^k)[seed, v], the personalised PageRank mass truncated at
+        walk_length steps (up to the factor restart and the k = 0 term).
+        restart_m: an integer in 0 .. 2^24 that overrides round(restart * 2^24), for tests.  no_compact: test switch (the 32-byte
+        first-order records).  A wrong dtype, rank, contiguity or device of seeds, num_walks / walk_length / top that are no integers or
+        outside the limits (1 .. 4096, 1 .. 4096 with a product of at most 4096, 1 .. 64), restart outside [0, 1]: TypeError before
+        the library is called."""
+        R, L, T = self._importance_shape(num_walks, walk_length, top)
+        rm = self._importance_restart(restart, restart_m)
+        t = self._seed_tensor(seeds, "importance_neighbors")
+        import torch
+        B = int(t.numel())
+        ids = torch.empty((B, T), dtype=torch.int32, device=t.device)
+        counts = torch.empty((B, T), dtype=torch.int32, device=t.device)
+        total = torch.empty((B,), dtype=torch.int32, device=t.device) if return_total else None
+        P = ImportanceParams(int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, int(base) & 0xFFFFFFFF, R, L, T, rm,
+                             (IMP_KEEP_SEED if keep_seed else 0) | (IMP_NO_COMPACT if no_compact else 0))
+        unknown = C.c_int64(0)
+        torch.cuda.current_stream(t.device).synchronize()                # the seeds are written before the handle's stream reads them
+        self._ck(lib().srw_importance_neighbors(self.h, C.c_void_p(t.data_ptr()), B, C.byref(P), C.c_void_p(ids.data_ptr()),
+                                                C.c_void_p(counts.data_ptr()), C.c_void_p(total.data_ptr()) if return_total else None,
+                                                C.byref(unknown)))
+        out = (ids, counts) + ((total,) if return_total else ()) + ((unknown.value,) if return_unknown else ())
+        return out
 
     def walk_to_host(self, pinned=True, sources=None, **kw):
         """srw_walk_to_host: all num_walks iterations streamed into host buffers (kernel i overlaps the copy of i-1).

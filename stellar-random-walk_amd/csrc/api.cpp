@@ -512,6 +512,43 @@ int32_t srw_sample_neighbors(srw_handle *h, const void *d_seeds, int64_t n_seeds
   });
 }
 
+// ---- importance neighbours (importance.hip) ----
+int32_t srw_importance_neighbors(srw_handle *h, const void *d_seeds, int64_t n_seeds, const srw_importance_params *ip, void *d_ids,
+                                 void *d_counts, void *d_total, int64_t *n_unknown) {
+  if (!h || !ip) return SRW_ERR_INVALID;
+  return guarded(h, [&] {
+    need_population0(h, "srw_importance_neighbors");
+    if (h->cfg.world != 1) throw Error(SRW_ERR_INVALID, "srw_importance_neighbors needs a whole-graph handle (world == 1)");
+    need(h->g.loaded, "srw_importance_neighbors: no graph loaded");
+    need(ip->num_walks >= 1 && ip->num_walks <= 4096, "srw_importance_neighbors: num_walks must be in 1 .. 4096");
+    need(ip->walk_length >= 1 && ip->walk_length <= 4096, "srw_importance_neighbors: walk_length must be in 1 .. 4096");
+    need((int64_t)ip->num_walks * ip->walk_length <= 4096, "srw_importance_neighbors: num_walks * walk_length must not exceed 4096");
+    need(ip->top >= 1 && ip->top <= 64, "srw_importance_neighbors: top must be in 1 .. 64");
+    need(ip->restart_m <= (1u << 24), "srw_importance_neighbors: restart_m must be in 0 .. 2^24");
+    need((ip->flags & ~(SRW_IMP_KEEP_SEED | SRW_IMP_NO_COMPACT)) == 0, "srw_importance_neighbors: flags holds an unknown bit");
+    need(n_seeds >= 0 && n_seeds < ((int64_t)1 << 31), "srw_importance_neighbors: n_seeds must be in [0, 2^31)");
+    need((int64_t)ip->base + n_seeds <= ((int64_t)1 << 32), "srw_importance_neighbors: base + n_seeds must not exceed 2^32");
+    if (n_seeds == 0) { if (n_unknown) *n_unknown = 0; return; }     // an empty tensor's pointers are arbitrary; nothing to launch
+    need(d_seeds != nullptr, "srw_importance_neighbors: d_seeds is null");
+    need(d_ids != nullptr, "srw_importance_neighbors: d_ids is null");
+    need(d_counts != nullptr, "srw_importance_neighbors: d_counts is null");
+    struct { uintptr_t p, bytes; } buf[4];                           // the seeds, ids, counts and (if given) the totals
+    const uintptr_t row = (uintptr_t)n_seeds * (uintptr_t)ip->top * 4u;
+    buf[0].p = (uintptr_t)d_seeds; buf[0].bytes = (uintptr_t)n_seeds * 4u;
+    buf[1].p = (uintptr_t)d_ids; buf[1].bytes = row;
+    buf[2].p = (uintptr_t)d_counts; buf[2].bytes = row;
+    buf[3].p = (uintptr_t)d_total; buf[3].bytes = (uintptr_t)n_seeds * 4u;
+    const int nbuf = d_total ? 4 : 3;
+    for (int i = 0; i < nbuf; ++i) need((buf[i].p & 3u) == 0, "srw_importance_neighbors: a pointer is not aligned to 4 bytes");
+    for (int i = 1; i < nbuf; ++i)
+      for (int k = 0; k < i; ++k)
+        need(buf[i].p + buf[i].bytes <= buf[k].p || buf[k].p + buf[k].bytes <= buf[i].p,
+             "srw_importance_neighbors: an output overlaps the seeds or another output");
+    const int64_t unknown = importance_neighbors(h, (const int32_t *)d_seeds, n_seeds, *ip, (int32_t *)d_ids, (int32_t *)d_counts, (int32_t *)d_total);
+    if (n_unknown) *n_unknown = unknown;
+  });
+}
+
 int32_t srw_host_alloc(size_t bytes, void **out) {
   if (!out) return SRW_ERR_INVALID;
   *out = nullptr;

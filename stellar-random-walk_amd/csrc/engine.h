@@ -204,6 +204,7 @@ struct srw_handle {
   srw::DevBuf<unsigned long long> vc_slots;      // srw_path_vertex_counts: occurrences per slot [n_slots], then the ids that are no vertex [1]
   srw::DevBuf<unsigned long long> sgns_skipped;  // srw_sgns_step: windows skipped for an id that is no present vertex [1]; srw_vertex_rows: ids that are no vertex; srw_sample_neighbors: seeds that are no vertex
   srw::DevBuf<char> topk_scratch;                // srw_topk_rows: one pass's candidate lists, staged queries and the skip count (topk.hip)
+  srw::DevBuf<uint32_t> imp_visits;              // srw_importance_neighbors: the visits of one chunk of seeds [chunk][R * L], at most 1 GiB (importance.hip)
   int64_t walkers_per_iteration() const { return n_sources >= 0 ? n_sources : g.n_vertices; }
   const int32_t *start_verts() const { return n_sources >= 0 ? src_verts.p : g.verts.p; }
   // srw_cluster_set_sources: the entries of the cluster's list that THIS shard owns, in list order (shard_set_sources, sources.hip):
@@ -373,6 +374,12 @@ void run_walk_metapath(srw_handle *h, const srw_walk_params &P, const int32_t *p
 // that are no present vertex.  d_layers: host array of n_layers device pointers.  Builds the first-order tables on first use.
 int64_t sample_neighbors(srw_handle *h, const int32_t *d_seeds, int64_t n_seeds, const int32_t *fanouts, int32_t n_layers,
                          const srw_neighbor_params &np, int32_t *const *d_layers);
+
+// ---- importance.hip ----
+// srw_importance_neighbors behind its argument checks (api.cpp), on the handle's stream, two launches per chunk of seeds, complete on
+// return -> seeds that are no present vertex.  d_total may be null.  Builds the first-order tables on first use.
+int64_t importance_neighbors(srw_handle *h, const int32_t *d_seeds, int64_t n_seeds, const srw_importance_params &ip, int32_t *d_ids,
+                             int32_t *d_counts, int32_t *d_total);
 
 // ---- path_format.hip ----
 size_t format_capacity(int64_t n, int64_t stride, int32_t vmin, int32_t vmax);
